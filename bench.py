@@ -15,10 +15,12 @@ RCCL all-reduce(sum) of the gradient and an Adam step.
 value = global batch * K / max-over-ranks seconds.  `--model sd21|sdxl` run BASELINE configs 4 / 5 (768^2 / 1024^2,
 embedding 77 x 1024 / 77 x 2048); `--tokens 500` is the reference CLI default token count.
 
-Rank 0 prints ONE JSON line with `roofline` (the dominant kernel of the step), `roofline_attn_map` /
-`roofline_self_attn` (the attention kernels), all measured live with events on the launch stream, `collective_check`
-(the RCCL all-reduce proven at start-up) and, at N=1, `cpu_baseline` (the oracle's reference-order CPU step on the
-host cores, bounded sample).
+Rank 0 prints ONE JSON line: `value`, `ms_per_step` (one timed step) and `collective_check` (the RCCL all-reduce proven at
+start-up).  A plain run does nothing else: set-up, warm-up, the timed steps, the line.  `--full` adds every measurement
+beside the headline: `roofline` (the dominant kernel of the step), `roofline_attn_map` / `roofline_self_attn` (the
+attention kernels), all measured live with events on the launch stream, `f32_instr`, live counter traffic and, at N=1,
+`cpu_baseline` (the oracle's reference-order CPU step on the host cores, bounded sample) and `verify`.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -41,7 +43,7 @@ F32_MATRIX_PEAK_TF = 157.3     # fp32 MFMA == fp32 vector peak
 BF16_MATRIX_PEAK_TF = 2500.0   # dense bf16 MFMA (MI355X_MICROARCH.md; the 5 PF/s headline is 2:1 sparsity)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -81,7 +83,24 @@ def parse():
                     help="the step as a captured hipGraph (optimize.GraphedStep): auto = the product's rule (<= 2 images per rank)")
     ap.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark=True (MIOpen find)")
     ap.add_argument("--channels-last", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: during set-up the CPU baseline and oracle verify "
+                         "(verify gives the GPU model the host-drawn weights, so the timed step and --dump-outputs differ from a "
+                         "plain run's), after the timed steps the kernel rooflines, live counter traffic, the f32-instruction step, "
+                         "per-launch conv accounting, the MFMA issue-rate probe, the step from idle (a plain run: set-up, warm-up, "
+                         "timed steps, the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy: the embedding after its optimizer step "
+                         "and Adam's first moment (float32), the step's total / equivariance / sharpening loss (float64)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    needs_full = [f for f, on in (("--cpu-baseline " + a.cpu_baseline, a.cpu_baseline in ("on", "full", "sample")),
+                                  ("--verify on", a.verify == "on"), ("--traffic " + a.traffic, a.traffic in ("live", "file")),
+                                  ("--conv-log", bool(a.conv_log))) if on]
+    if needs_full and not a.full:
+        ap.error(f"{', '.join(needs_full)}: measurements beside the headline run only with --full")
+    return a
 
 
 def map_kernel_roofline(ops, B, T, R, iters, device, layer_dims=None, top_k=10):
@@ -551,6 +570,18 @@ def verify_against_oracle(ldm_cpu, ldm, controller, a, dev):
             "cpu_step_seconds": cpu_s}
 
 
+def dump_outputs(out_dir, ctx, opt, step_out):
+    """What a caller of the timed step receives from its last call: the embedding after that step's optimizer update
+    ([1, T, width] float32), Adam's first moment of the embedding gradient after it (same shape; linear in the gradients,
+    so it carries their run-to-run spread without the normalisation that amplifies it in the embedding) and the (total,
+    equivariance, sharpening) losses the step returned (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "embedding.npy"), ctx.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "adam_exp_avg.npy"), opt.state[ctx]["exp_avg"].detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "losses.npy"), torch.stack([v.detach().reshape(()) for v in step_out]).double().cpu().numpy())
+
+
 NATIVE_SIZE = {"sd15": 512, "sd21": 768, "sdxl": 1024, "tiny": 128, "tiny-sd21": 128, "tiny-sdxl": 128}
 MODEL_LABEL = {"sd15": "SD1.5", "sd21": "SD2.1", "sdxl": "SDXL"}
 CONFIG_NAME = {"sd15": "BASELINE config 2", "sd21": "BASELINE config 4", "sdxl": "BASELINE config 5"}
@@ -626,8 +657,8 @@ def main():
 
     t_build = time.time()
     cpu_stats, t_cpu = None, 0.0
-    want_cpu = a.cpu_baseline in ("on", "full", "sample") or (a.cpu_baseline == "auto" and world == 1 and a.model == "sd15")
-    want_verify = a.verify == "on" or (a.verify == "auto" and want_cpu)
+    want_cpu = a.full and (a.cpu_baseline in ("on", "full", "sample") or (a.cpu_baseline == "auto" and world == 1 and a.model == "sd15"))
+    want_verify = a.full and (a.verify == "on" or (a.verify == "auto" and want_cpu))
     ldm_cpu = None
     if (want_cpu or want_verify) and rank == 0:
         # the CPU leg gets its own host-side instance (seeded host draw)
@@ -710,13 +741,17 @@ def main():
     torch.cuda.synchronize()
     D.barrier()
     elapsed = time.perf_counter() - t0
-    # one more step from an idle GPU: when does the launch thread return, when is the GPU done?  (launch_ms < total_ms: the
-    # step is GPU-bound and the host has slack; launch_ms ~ total_ms: launch-bound -- what a captured hipGraph would remove)
-    ti = time.perf_counter()
-    one_step()
-    t_issue = time.perf_counter() - ti
-    torch.cuda.synchronize()
-    t_idle_total = time.perf_counter() - ti
+    last_loss = float(last[0])                                    # read now: a captured step's outputs are views of a static buffer
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ctx, opt, last)
+    if a.full:
+        # one more step from an idle GPU: when does the launch thread return, when is the GPU done?  (launch_ms < total_ms: the
+        # step is GPU-bound and the host has slack; launch_ms ~ total_ms: launch-bound -- what a captured hipGraph would remove)
+        ti = time.perf_counter()
+        one_step()
+        t_issue = time.perf_counter() - ti
+        torch.cuda.synchronize()
+        t_idle_total = time.perf_counter() - ti
     tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -729,7 +764,8 @@ def main():
         torch.distributed.all_reduce(hi, op=torch.distributed.ReduceOp.MAX)
         coll["embedding_identical_on_all_ranks"] = bool(torch.equal(lo, hi))
 
-    if rank == 0:
+    full = None
+    if rank == 0 and a.full:
         B = 2 * per_rank                                          # rows per fused-map launch (both views)
         ldims = hooked_layer_dims(a.model, image_size)
         kt, fwd_bytes, bwd_bytes, flops_equiv = map_kernel_roofline(ops, B, a.tokens, a.res, a.kernel_iters, dev, ldims, a.top_k)
@@ -773,7 +809,6 @@ def main():
             ctx.grad = None
         conv_all = conv_step_accounting(ops, local_step, a.conv_log or None)
         ach = fwd_bytes / kt["fwd"] / 1e9
-        value = global_batch * a.steps / elapsed
         try:                                                      # measurement aid from tools/csrc/libskp_lab.so (not the product library)
             issue1, issue2 = ops.mfma_issue_rate(1, device=dev), ops.mfma_issue_rate(2, device=dev)
         except Exception as e:                                    # noqa: BLE001 -- the line of record does not depend on the probe
@@ -801,34 +836,7 @@ def main():
                 map_bwd_traffic = {"total": sum(bwd_parts.values()), "by_kernel": bwd_parts}
         elif a.traffic == "off":
             conv_traffic = conv_src = map_traffic = map_src = None
-        cfg_name = CONFIG_NAME.get(a.model, "reduced-width test model")
-        if a.model == "sd15" and a.scaling == "strong":
-            cfg_name = "BASELINE config 3 (fixed global batch)"
-        line = {
-            "metric": f"images/sec for token-optimization step ({MODEL_LABEL.get(a.model, a.model)}, {image_size}^2, K={a.top_k} kpts)",
-            "value": value, "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling,
-            "scaling_definition": ("weak: every rank processes images_per_rank images per optimizer step, the global batch "
-                                   "is images_per_rank x N" if a.scaling == "weak" else
-                                   "strong: the global batch is fixed (global_batch images per optimizer step), each rank "
-                                   "processes global_batch / N of them"),
-            "vs_baseline": None,
-            "dtype": DTYPE_LINE,
-            "data": "synthetic",
-            **({"experiment": "cache_latents: the un-warped views' latents are reused from the first epoch over the "
-                              f"{len(data)}-image synthetic set (half of each step's VAE work skipped); NOT the bench of record"}
-               if a.cache_latents else {}),
-            "config": {"workload": f"{cfg_name}: T={a.tokens} R={a.res} K={a.top_k}/{a.candidates} {a.model} {image_size}^2 "
-                                   f"{per_rank} img/rank x 2 views fp32",
-                       "workload_detail": f"{a.model} architecture UNet+VAE (seeded synthetic weights), {image_size}x{image_size}, batch "
-                                          f"{per_rank} images/rank/step x 2 views, T={a.tokens} tokens x {width}, R={a.res}, "
-                                          f"top_k={a.top_k} of {a.candidates}, fp32 end to end",
-                       "global_batch": global_batch, "images_per_rank": per_rank, "tokens": a.tokens, "embedding_dim": width,
-                       "feature_upsample_res": a.res, "parallelism": f"dp{world}",
-                       "kept_across_steps": "functions of the frozen weights and the fixed timestep only: transformed convolution "
-                                            "filters, summed biases, the time embedding and the per-resnet offsets derived from it "
-                                            "(ldm/fused.py); nothing that depends on an image, the noise or the embedding "
-                                            "(latents are re-encoded every step: --cache-latents is a separate experiment line)"},
+        full = {
             # dominant kernel of the step by time: the Winograd conv of the frozen blocks, priced on the
             # fp32 matrix-core peak with the FLOPs it actually executes (direct-form FLOPs / 4)
             "roofline": {"kernel": f"skp_wino4_conv_c128_kernel<STATS={'true' if cv_folded else 'false'}, GNF={'true' if cv_folded else 'false'}> "
@@ -884,18 +892,54 @@ def main():
                                         "self_attn_bwd_fp32_equiv_over_fp32_peak": sa_b / sa["bwd"] / 1e12 / F32_MATRIX_PEAK_TF},
             "f32_instr": f32_instr,
             "traffic_live_kernels": sorted(live) if live else None,
-            "cpu_baseline": cpu_stats, "verify": verify, "collective_check": coll,
-            "loss": float(last[0]), "setup_s": t_build, "cpu_baseline_s": t_cpu,
+            "cpu_baseline": cpu_stats, "verify": verify, "cpu_baseline_s": t_cpu,
+            "step_from_idle": {"launch_thread_returns_ms": t_issue * 1e3, "gpu_done_ms": t_idle_total * 1e3},
+        }
+        if full["roofline"]["traffic"]:
+            full["roofline"]["hbm_gbs_at_traffic"] = full["roofline"]["traffic"] / cv_t / 1e9
+
+    if rank == 0:
+        cfg_name = CONFIG_NAME.get(a.model, "reduced-width test model")
+        if a.model == "sd15" and a.scaling == "strong":
+            cfg_name = "BASELINE config 3 (fixed global batch)"
+        line = {
+            "metric": f"images/sec for token-optimization step ({MODEL_LABEL.get(a.model, a.model)}, {image_size}^2, K={a.top_k} kpts)",
+            "value": global_batch * a.steps / elapsed, "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling,
+            "scaling_definition": ("weak: every rank processes images_per_rank images per optimizer step, the global batch "
+                                   "is images_per_rank x N" if a.scaling == "weak" else
+                                   "strong: the global batch is fixed (global_batch images per optimizer step), each rank "
+                                   "processes global_batch / N of them"),
+            "vs_baseline": None,
+            "dtype": DTYPE_LINE,
+            "data": "synthetic",
+            **({"experiment": "cache_latents: the un-warped views' latents are reused from the first epoch over the "
+                              f"{len(data)}-image synthetic set (half of each step's VAE work skipped); NOT the bench of record"}
+               if a.cache_latents else {}),
+            "config": {"workload": f"{cfg_name}: T={a.tokens} R={a.res} K={a.top_k}/{a.candidates} {a.model} {image_size}^2 "
+                                   f"{per_rank} img/rank x 2 views fp32",
+                       "workload_detail": f"{a.model} architecture UNet+VAE (seeded synthetic weights), {image_size}x{image_size}, batch "
+                                          f"{per_rank} images/rank/step x 2 views, T={a.tokens} tokens x {width}, R={a.res}, "
+                                          f"top_k={a.top_k} of {a.candidates}, fp32 end to end",
+                       "global_batch": global_batch, "images_per_rank": per_rank, "tokens": a.tokens, "embedding_dim": width,
+                       "feature_upsample_res": a.res, "parallelism": f"dp{world}",
+                       "kept_across_steps": "functions of the frozen weights and the fixed timestep only: transformed convolution "
+                                            "filters, summed biases, the time embedding and the per-resnet offsets derived from it "
+                                            "(ldm/fused.py); nothing that depends on an image, the noise or the embedding "
+                                            "(latents are re-encoded every step: --cache-latents is a separate experiment line)"},
+            "collective_check": coll,
+            "loss": last_loss, "setup_s": t_build,
             "launch_thread_cpu_ms_per_step": c_launch / a.steps * 1e3,
             "captured_step": ({"on": True, "what": "forward + losses + backward of a step replayed from one hipGraph (optimize.GraphedStep; inputs, "
                                                    "noise and affines refreshed in static buffers before every replay); all-reduce + Adam eager",
                                "group_sizes_captured": sorted(k for k, v in graphed.state.items() if v != "eager" and v.get("graph") is not None)}
                               if graphed is not None else {"on": False}),
-            "step_from_idle": {"launch_thread_returns_ms": t_issue * 1e3, "gpu_done_ms": t_idle_total * 1e3}, "prewarm_steps": 1, "gemm_tunableop_file": bool(gemm_tuned),
+            "prewarm_steps": 1, "gemm_tunableop_file": bool(gemm_tuned),
             "weights_init": weights_init,
+            "full": a.full,
         }
-        if line["roofline"]["traffic"]:
-            line["roofline"]["hbm_gbs_at_traffic"] = line["roofline"]["traffic"] / cv_t / 1e9
+        if full:
+            line.update(full)
         print(json.dumps(line), flush=True)
     D.barrier()
     if world > 1:

@@ -515,6 +515,18 @@ def test_bench_self_launches_when_no_launcher_environment():
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_extra_measurements_only_with_full():
+    """A plain bench run is the headline alone: `--full` is off by default, and asking for a measurement beside the
+    headline (CPU baseline, verify, counter traffic, conv launch log) without it is an error, not a silent no-op."""
+    import bench
+    a = bench.parse(["--steps", "5", "--dump-outputs", "out"])
+    assert a.full is False and a.steps == 5 and a.dump_outputs == "out"
+    assert bench.parse(["--full", "--cpu-baseline", "sample", "--verify", "on", "--traffic", "live"]).full
+    for extra in (["--cpu-baseline", "on"], ["--verify", "on"], ["--traffic", "file"], ["--conv-log", "x.json"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(extra)
+
+
 def test_fused_attn_materialize_under_autograd_names_the_missing_rebind():
     """A handle whose q / k carry gradient history must not be materialised while autograd records (the reference's
     `optimize_embedding` kept on a re-bound `load_ldm`): the error names the second re-bind instead of autograd's generic

@@ -3,7 +3,7 @@
 steady-state window: the last N optimisation steps, delimited by the Adam (multi_tensor_apply) launches.
 usage: step_breakdown.py <run_kernel_trace.csv> [N=2] [conv_log.json]
 
-With the launch list `bench.py --conv-log conv_log.json` wrote (shape + algorithmic FLOPs of every Winograd F(4x4,3x3) call of
+With the launch list `bench.py --full --conv-log conv_log.json` wrote (shape + algorithmic FLOPs of every Winograd F(4x4,3x3) call of
 one step, in launch order) the trace's `skp_wino4_conv*` launches are matched to it by position and the TIME-WEIGHTED fraction
 of the fp32 matrix peak over ALL `skp_wino4_*` kernels of a step (K-split reductions included in the time) is printed:
 sum of FLOPs / sum of kernel time / 157.3 TF/s -- the figure bench.py carries as roofline.conv_all_launches.frac."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The two roofline kernels of bench.py at their bench launch shapes, a few launches each and nothing else: the workload
-`bench.py --traffic live` runs under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, counters only) to
+`bench.py --full --traffic live` runs under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, counters only) to
 read the HBM traffic of THIS build on THIS box.    python tools/traffic_probe.py --rows 8 --tokens 77 --res 128 --image-size 512"""
 import argparse
 import os
