@@ -46,29 +46,17 @@ def _resnet_forward(m: ResnetBlock2D):
     return forward
 
 
-def _frozen_tag(*params):
-    """Identity of frozen parameters (None when one of them takes gradients: nothing derived from it may be kept)."""
-    if any(p is not None and p.requires_grad for p in params):
-        return None
-    return tuple((p._version, p.data_ptr()) for p in params if p is not None)
-
-
 def _norm2_offset(m: ResnetBlock2D, rows: int, temb):
     """Per-(row, channel) offset in front of norm2: conv1.bias + time_emb_proj(silu(temb)), contiguous [rows, C].  With the
     time path kept by `_time_path` below the SAME `temb` tensor arrives every step, and the offset of a frozen block is kept
-    with it (4 small launches per block and step otherwise)."""
-    tag = _frozen_tag(m.conv1.bias, *(m.time_emb_proj.parameters() if m.time_emb_proj is not None else ()))
-    hit = m.__dict__.get("_skp_off")
-    if (hit is not None and tag is not None and hit[0] is temb and hit[1] == (tag, rows)
-            and (temb is None or (hit[2] == temb._version and not temb.requires_grad))):
-        return hit[3]
-    off = m.conv1.bias[None, :].expand(rows, -1)
-    if m.time_emb_proj is not None and temb is not None:
-        off = off + m.time_emb_proj(F.silu(temb))
-    off = off.contiguous()
-    if tag is not None and not off.requires_grad:
-        m.__dict__["_skp_off"] = (temb, (tag, rows), None if temb is None else temb._version, off)
-    return off
+    with it, one per row count (4 small launches per block and step otherwise)."""
+    def build():
+        off = m.conv1.bias[None, :].expand(rows, -1)
+        if m.time_emb_proj is not None and temb is not None:
+            off = off + m.time_emb_proj(F.silu(temb))
+        return off.contiguous()
+    proj = m.time_emb_proj.parameters() if m.time_emb_proj is not None else ()
+    return ops.cached(m, ("norm2_offset", rows), (m.conv1.bias, *proj, temb), build)
 
 
 def _time_path(m: UNet2DConditionModel):
@@ -79,7 +67,7 @@ def _time_path(m: UNet2DConditionModel):
 
     def time_path(sample, timestep, added_cond_kwargs=None):
         host = not torch.is_tensor(timestep) or (timestep.device.type == "cpu" and timestep.numel() <= 64)
-        tag = _frozen_tag(*m.time_embedding.parameters(), *(m.add_embedding.parameters() if m.add_embedding is not None else ()))
+        tag = ops.frozen_tag([*m.time_embedding.parameters(), *(m.add_embedding.parameters() if m.add_embedding is not None else ())])
         if not host or tag is None or added_cond_kwargs is not None:
             return orig(sample, timestep, added_cond_kwargs)
         vals = tuple(float(v) for v in (timestep.reshape(-1).tolist() if torch.is_tensor(timestep) else [timestep]))
@@ -92,7 +80,7 @@ def _time_path(m: UNet2DConditionModel):
             with torch.no_grad():
                 hit = orig(sample, timestep, added_cond_kwargs)
             memo[key] = hit
-        return hit
+        return ops.handed_out(hit)              # (a captured step holds it: the memo may drop it)
     return time_path
 
 
@@ -101,14 +89,7 @@ def _summed_bias(m: ResnetBlock2D):
     b2, bs = m.conv2.bias, m.conv_shortcut.bias
     if bs is None:
         return b2
-    if b2.requires_grad or bs.requires_grad:
-        return b2 + bs
-    tag = (b2._version, bs._version, b2.data_ptr(), bs.data_ptr())
-    hit = m.__dict__.get("_skp_bias_sum")
-    if hit is None or hit[0] != tag:
-        hit = (tag, (b2.detach() + bs.detach()))
-        m.__dict__["_skp_bias_sum"] = hit
-    return hit[1]
+    return ops.cached(m, "bias_sum", (b2, bs), lambda: b2 + bs)
 
 
 def _transformer_forward(m: Transformer2DModel):
@@ -200,12 +181,8 @@ def _vae_encode(m):
     orig = m.encode
     from .vae import DiagonalGaussianDistribution
 
-    def composed():
+    def compose():
         enc, q = m.encoder, m.quant_conv
-        tag = _frozen_tag(enc.conv_out.weight, enc.conv_out.bias, q.weight, q.bias)
-        hit = m.__dict__.get("_skp_tail")
-        if hit is not None and tag is not None and hit[0] == tag:
-            return hit[1], hit[2]
         with torch.no_grad():
             wq = q.weight.flatten(1).double()                                   # [8, 8]
             w = (wq @ enc.conv_out.weight.double().flatten(1)).reshape(q.weight.shape[0], *enc.conv_out.weight.shape[1:])
@@ -214,16 +191,16 @@ def _vae_encode(m):
             wp = torch.zeros(32, *w.shape[1:], device=w.device, dtype=torch.float32)
             bp = torch.zeros(32, device=w.device, dtype=torch.float32)
             wp[:co], bp[:co] = w.float(), b.float()
-        if tag is not None:
-            m.__dict__["_skp_tail"] = (tag, wp, bp)
         return wp, bp
+
+    def tail_params():
+        return (m.encoder.conv_out.weight, m.encoder.conv_out.bias, m.quant_conv.weight, m.quant_conv.bias)
 
     def encode(x):
         enc, q = m.encoder, m.quant_conv
         ok = (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and q.kernel_size == (1, 1)
               and q.weight.shape[0] <= 32 and enc.conv_out.kernel_size == (3, 3) and enc.conv_out.padding == (1, 1)
-              and _frozen_tag(enc.conv_out.weight, enc.conv_out.bias, q.weight, q.bias) is not None
-              and q.bias is not None and enc.conv_out.bias is not None)
+              and q.bias is not None and enc.conv_out.bias is not None and not any(p.requires_grad for p in tail_params()))
         if not ok:
             return orig(x)
         h = enc.conv_in(x)
@@ -232,7 +209,7 @@ def _vae_encode(m):
         h = enc.mid_block(h)
         if not (ops.group_norm_supported(h, enc.conv_norm_out.num_groups) and ops.conv3x3_wanted(h.shape, (32, h.shape[1], 3, 3))):
             return {"latent_dist": DiagonalGaussianDistribution(q(enc.conv_out(F.silu(enc.conv_norm_out(h)))))}
-        wp, bp = composed()
+        wp, bp = ops.cached(m, "vae_tail", tail_params(), compose)
         h = ops.group_norm_silu(h, enc.conv_norm_out)
         y = ops.conv3x3_auto(h, wp, bp)
         return {"latent_dist": DiagonalGaussianDistribution(y[:, :q.weight.shape[0]])}

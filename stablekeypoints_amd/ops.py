@@ -6,6 +6,8 @@ stream.  No op has an eager/CPU fallback: a non-CUDA tensor raises.
 """
 from __future__ import annotations
 
+import contextlib
+import weakref
 from typing import List, Sequence, Tuple
 
 import torch
@@ -24,6 +26,71 @@ def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
     if t.dtype != torch.float32:
         raise RuntimeError(f"{name}: expected float32, got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(query: str, *args, device):
+    """Scratch for the launch that follows: `query(*args)` bytes as ceil(bytes / 4) floats, None (a null pointer) for 0 bytes;
+    a negative answer raises."""
+    nbytes = int(getattr(N.lib(), query)(*args))
+    if nbytes < 0:
+        N.check(nbytes, query)
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32) if nbytes else None
+
+
+# ---------------------------------------------------------------------------------------------
+# values derived from frozen tensors (transformed filters, stacked weights, folded offsets / biases)
+# ---------------------------------------------------------------------------------------------
+# Built once and kept on an owner object (a Parameter or a module), so an entry dies with its owner.  An entry is reused while
+# every input it was built from is the same object with the same storage, version, device and dtype; a changed input replaces
+# the entry under its key; an input that takes gradients keeps nothing.  While a step is captured (optimize.GraphedStep) every
+# value handed out is also held by the recording, for as long as the graph that reads it lives.
+_recording = None
+
+
+def frozen_tag(inputs):
+    """(storage, version, device, dtype) of every input that is not None, or None when one of them takes gradients (nothing
+    derived from it may be kept)."""
+    tag = []
+    for t in inputs:
+        if t is not None:
+            if t.requires_grad:
+                return None
+            tag.append((t.data_ptr(), t._version, t.device, t.dtype))
+    return tuple(tag)
+
+
+def handed_out(value):
+    if _recording is not None:
+        _recording.append(value)
+    return value
+
+
+@contextlib.contextmanager
+def recording():
+    """-> a list that receives every kept value handed out inside the block."""
+    global _recording
+    prev, _recording = _recording, []
+    try:
+        yield _recording
+    finally:
+        _recording = prev
+
+
+def cached(owner, key, inputs, build):
+    """`build()` -- a tensor or tuple of tensors that depends on `inputs` (None entries are skipped) and on what `key` names --
+    kept on `owner`."""
+    tag = frozen_tag(inputs)
+    if tag is None:
+        return build()
+    store = owner.__dict__.setdefault("_skp_cache", {})
+    hit = store.get(key)
+    if hit is None or hit[0] != tag or not all(r() is t for r, t in zip(hit[1], (t for t in inputs if t is not None))):
+        hit = store[key] = (tag, [weakref.ref(t) for t in inputs if t is not None], build())
+    return handed_out(hit[2])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -123,16 +190,13 @@ def _map_bwd(S, dS, sides, B, H, T, R, dM, lse):
     L, ldt = len(S), S[0].shape[-1]
     si, _k3 = N.int_array(sides)
     lib, st = N.lib(), _stream()
-    nbytes = lib.skp_attn_map_bwd_workspace(si, L, B, H, T if T <= TOKEN_GROUP else GROUP_STEP, R)
-    if nbytes < 0:
-        N.check(int(nbytes), "skp_attn_map_bwd_workspace")
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    ws = _workspace("skp_attn_map_bwd_workspace", si, L, B, H, T if T <= TOKEN_GROUP else GROUP_STEP, R, device=dev)
 
     def launch(t0, t1, mode, dot):
         sp, _k1 = N.ptr_array([t.data_ptr() + 4 * t0 for t in S])
         dp, _k2 = N.ptr_array([t.data_ptr() + 4 * t0 for t in dS])
         N.check(lib.skp_attn_map_bwd_ex_f32(sp, dp, si, L, B, H, t1 - t0, R, dM.data_ptr() + 4 * t0 * R * R,
-                                            lse.data_ptr(), ws.data_ptr(), dot.data_ptr() if dot is not None else None,
+                                            lse.data_ptr(), _ptr(ws), _ptr(dot),
                                             ldt, T * R * R, mode, st), "skp_attn_map_bwd_ex_f32")
 
     if T <= TOKEN_GROUP:
@@ -184,28 +248,15 @@ def _map_bwd_sparse(S, sides, B, H, T, R, sel, G, lse):
     G = _dev(G, "G")
     dS = [torch.empty_like(s_) for s_ in S]
     si, _k0 = N.int_array(sides)
-    lib = N.lib()
     if MAP_BWD_MODE != "sweep" and T <= COL_MAX_T and map_bwd_col_supported(sides, K, R, T, H):
-        nbytes = lib.skp_attn_map_bwd_col_workspace(si, L, B, H, T, R, K)
-        if nbytes < 0:
-            N.check(int(nbytes), "skp_attn_map_bwd_col_workspace")
-        ws = torch.empty((nbytes + 3) // 4, device=G.device, dtype=torch.float32)
-        sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
-        dp, _k2 = N.ptr_array([t.data_ptr() for t in dS])
-        N.check(lib.skp_attn_map_bwd_col_f32(sp, dp, si, L, B, H, T, R, sel.data_ptr(), G.data_ptr(), K, lse.data_ptr(),
-                                             ws.data_ptr(), ldt, _stream()), "skp_attn_map_bwd_col_f32")
-        if ldt > (T + 15) // 16 * 16:
-            for d_ in dS:
-                d_[..., (T + 15) // 16 * 16:] = 0
-        return dS
-    nbytes = lib.skp_attn_map_bwd_sparse_workspace(si, L, B, H, T, R, K)
-    if nbytes < 0:
-        N.check(int(nbytes), "skp_attn_map_bwd_sparse_workspace")
-    ws = torch.empty((nbytes + 3) // 4, device=G.device, dtype=torch.float32)
+        query, name = "skp_attn_map_bwd_col_workspace", "skp_attn_map_bwd_col_f32"              # column sweep
+    else:
+        query, name = "skp_attn_map_bwd_sparse_workspace", "skp_attn_map_bwd_sparse_f32"        # token-major sweep
+    ws = _workspace(query, si, L, B, H, T, R, K, device=G.device)
     sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
     dp, _k2 = N.ptr_array([t.data_ptr() for t in dS])
-    N.check(lib.skp_attn_map_bwd_sparse_f32(sp, dp, si, L, B, H, T, R, sel.data_ptr(), G.data_ptr(), K, lse.data_ptr(),
-                                            ws.data_ptr(), ldt, _stream()), "skp_attn_map_bwd_sparse_f32")
+    N.check(getattr(N.lib(), name)(sp, dp, si, L, B, H, T, R, sel.data_ptr(), G.data_ptr(), K, lse.data_ptr(), _ptr(ws), ldt,
+                                   _stream()), name)
     if ldt > (T + 15) // 16 * 16:                              # gap columns of a wider logits buffer: never read, keep finite
         for d_ in dS:
             d_[..., (T + 15) // 16 * 16:] = 0
@@ -579,10 +630,9 @@ class CrossAttnFn(torch.autograd.Function):
         dq = torch.empty_like(q)
         dk = torch.empty(B, T, C, device=q.device, dtype=torch.float32)
         dv = torch.empty_like(dk)
-        nbytes = N.lib().skp_cross_attn_bwd_workspace(B, heads, Nq, T, C // heads)
-        ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+        ws = _workspace("skp_cross_attn_bwd_workspace", B, heads, Nq, T, C // heads, device=q.device)
         N.check(N.lib().skp_cross_attn_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+                                               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _ptr(ws),
                                                B, Bk, heads, Nq, T, C // heads, scale, _stream()),
                 "skp_cross_attn_bwd_f32")
         if Bk == 1 and B > 1:
@@ -682,14 +732,20 @@ GN_FUSED_STATS = True
 GN_FORK = True
 
 
-def group_norm_silu(x, norm: torch.nn.GroupNorm, off=None, silu: bool = True):
-    """GroupNorm(+offset)(+SiLU).  If `x` is the output of one of this library's convolutions that left block sums
-    behind (`x._skp_blocks`, set by conv3x3_auto / conv3x3_s2), the statistics pass over `x` is skipped."""
+def _blocks(x):
+    """(block sums, blocks per image, pixels per block) that x's producing convolution left behind (`x._skp_blocks`, set by
+    conv3x3_auto / conv3x3_s2 / conv3x3_small / conv3x3_gn_silu), or None when there are none or they do not describe x."""
     blocks = getattr(x, "_skp_blocks", None) if GN_FUSED_STATS else None
     if blocks is not None and (blocks[0].shape[0] != x.shape[0] or blocks[0].shape[1] != x.shape[1]
                                or blocks[1] * blocks[2] != x.shape[2] * x.shape[3]):
-        blocks = None
-    return GroupNormSiLUFn.apply(x, off, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, blocks)
+        return None
+    return blocks
+
+
+def group_norm_silu(x, norm: torch.nn.GroupNorm, off=None, silu: bool = True):
+    """GroupNorm(+offset)(+SiLU).  If `x` is the output of one of this library's convolutions that left block sums
+    behind (`_blocks`), the statistics pass over `x` is skipped."""
+    return GroupNormSiLUFn.apply(x, off, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, _blocks(x))
 
 
 def group_norm_silu_fork(x, norm: torch.nn.GroupNorm, off=None, silu: bool = True):
@@ -697,11 +753,7 @@ def group_norm_silu_fork(x, norm: torch.nn.GroupNorm, off=None, silu: bool = Tru
     carry (or with the switch off) x' is x itself and nothing changes."""
     if not (GN_FORK and torch.is_grad_enabled() and x.requires_grad):
         return group_norm_silu(x, norm, off=off, silu=silu), x
-    blocks = getattr(x, "_skp_blocks", None) if GN_FUSED_STATS else None
-    if blocks is not None and (blocks[0].shape[0] != x.shape[0] or blocks[0].shape[1] != x.shape[1]
-                               or blocks[1] * blocks[2] != x.shape[2] * x.shape[3]):
-        blocks = None
-    return GroupNormSiLUForkFn.apply(x, off, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, blocks)
+    return GroupNormSiLUForkFn.apply(x, off, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, _blocks(x))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -719,33 +771,52 @@ def self_attn_supported(C: int, heads: int) -> bool:
 # kernels everywhere (bench.py times that step beside the line as `f32_instr`).
 FLASH_SPLIT = True
 FLASH_SPLIT_MIN_KEYS = 1024
-def flash_split_ok(B, Bk, heads, Nq, Nk, d) -> bool:
-    return Nk >= FLASH_SPLIT_MIN_KEYS and bool(N.lib().skp_flash_attn_fwd_split_ok(B, Bk, heads, Nq, Nk, d))
 
 
-def _flash_fwd_split(q, k, v, out, lse, heads, scale):
+def flash_split_ok(B, Bk, heads, Nq, Nk, d, backward=False) -> bool:
+    """The split-bf16 kernels take this flash launch (the fp32-instruction kernels every other one)."""
+    ok = N.lib().skp_flash_attn_bwd_split_ok if backward else N.lib().skp_flash_attn_fwd_split_ok
+    return FLASH_SPLIT and Nk >= FLASH_SPLIT_MIN_KEYS and bool(ok(B, Bk, heads, Nq, Nk, d))
+
+
+def _flash_fwd(q, k, v, out, lse, heads, scale, split=None):
+    """out, lse (natural log) of softmax(scale q k^T) v; `split` forces the kernels, None: `flash_split_ok`."""
     B, Nq, C = q.shape
     Bk, Nk, _ = k.shape
-    nbytes = N.lib().skp_flash_attn_fwd_split_workspace(B, Bk, heads, Nq, Nk, C // heads)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    N.check(N.lib().skp_flash_attn_fwd_split_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), ws.data_ptr(),
-                                                 B, Bk, heads, Nq, Nk, C // heads, scale, _stream()), "skp_flash_attn_fwd_split_f32")
+    shape = (B, Bk, heads, Nq, Nk, C // heads)
+    if split is None:
+        split = flash_split_ok(*shape)
+    if split:
+        ws = _workspace("skp_flash_attn_fwd_split_workspace", *shape, device=q.device)
+        N.check(N.lib().skp_flash_attn_fwd_split_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                     _ptr(ws), *shape, float(scale), _stream()), "skp_flash_attn_fwd_split_f32")
+    else:
+        N.check(N.lib().skp_flash_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                               *shape, float(scale), _stream()), "skp_flash_attn_fwd_f32")
 
 
-def _flash_bwd_split(q, k, v, out, dout, lse, dq, dk, dv, heads, scale):
+def _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, ld, split=None):
+    """dq, dk, dv of `_flash_fwd` into the device addresses dq / dk / dv, rows `ld` floats apart (H*d: dense tensors; dk / dv
+    hold B rows even for a shared k / v); `split` as in `_flash_fwd`."""
     B, Nq, C = q.shape
-    nbytes = N.lib().skp_flash_attn_bwd_split_workspace(B, B, heads, Nq, Nq, C // heads)
-    ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-    N.check(N.lib().skp_flash_attn_bwd_split_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
-                                                 dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, B, heads, Nq, Nq, C // heads,
-                                                 float(scale), _stream()), "skp_flash_attn_bwd_split_f32")
+    Bk, Nk, _ = k.shape
+    shape = (B, Bk, heads, Nq, Nk, C // heads)
+    if split is None:
+        split = flash_split_ok(*shape, backward=True)
+    if split:
+        query, name = "skp_flash_attn_bwd_split_workspace", "skp_flash_attn_bwd_split_ld_f32"
+    else:
+        query, name = "skp_flash_attn_bwd_workspace", "skp_flash_attn_bwd_ld_f32"
+    ws = _workspace(query, *shape, device=q.device)
+    N.check(getattr(N.lib(), name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                   dq, dk, dv, _ptr(ws), *shape, float(scale), int(ld), _stream()), name)
 
 
 def flash_attn_bwd_split(q, k, v, out, dout, lse, heads: int, scale: float):
     """Direct entry (tests / tools): (dq, dk, dv) of the split backward (self-attention shapes)."""
     q, k, v, out, dout, lse = (_dev(t_, "t") for t_ in (q, k, v, out, dout, lse))
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    _flash_bwd_split(q, k, v, out, dout, lse, dq, dk, dv, heads, scale)
+    _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.shape[2], split=True)
     return dq, dk, dv
 
 
@@ -754,7 +825,7 @@ def flash_attn_fwd_split(q, k, v, heads: int, scale: float):
     q, k, v = _dev(q, "q"), _dev(k, "k"), _dev(v, "v")
     out = torch.empty_like(q)
     lse = torch.empty(q.shape[0], heads, q.shape[1], device=q.device, dtype=torch.float32)
-    _flash_fwd_split(q, k, v, out, lse, heads, float(scale))
+    _flash_fwd(q, k, v, out, lse, heads, scale, split=True)
     return out, lse
 
 
@@ -766,15 +837,9 @@ class FlashAttnFn(torch.autograd.Function):
     def forward(ctx, q, k, v, heads: int, scale: float):
         q, k, v = _dev(q, "q"), _dev(k, "k"), _dev(v, "v")
         B, Nq, C = q.shape
-        Bk, Nk, _ = k.shape
         out = torch.empty_like(q)
         lse = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
-        if FLASH_SPLIT and flash_split_ok(B, Bk, heads, Nq, Nk, C // heads):
-            _flash_fwd_split(q, k, v, out, lse, heads, float(scale))
-        else:
-            N.check(N.lib().skp_flash_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                                   B, Bk, heads, Nq, Nk, C // heads, float(scale), _stream()),
-                    "skp_flash_attn_fwd_f32")
+        _flash_fwd(q, k, v, out, lse, heads, scale)
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.meta = (heads, float(scale))
         return out
@@ -789,16 +854,7 @@ class FlashAttnFn(torch.autograd.Function):
         dq = torch.empty_like(q)
         dk = torch.empty(B, Nk, C, device=q.device, dtype=torch.float32)
         dv = torch.empty_like(dk)
-        if FLASH_SPLIT and Nk >= FLASH_SPLIT_MIN_KEYS and N.lib().skp_flash_attn_bwd_split_ok(B, Bk, heads, Nq, Nk, C // heads):
-            _flash_bwd_split(q, k, v, out, dout, lse, dq, dk, dv, heads, scale)
-            return dq, dk, dv, None, None
-        nbytes = N.lib().skp_flash_attn_bwd_workspace(B, Bk, heads, Nq, Nk, C // heads)
-        if nbytes < 0:
-            N.check(int(nbytes), "skp_flash_attn_bwd_workspace")
-        ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-        N.check(N.lib().skp_flash_attn_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(),
-                                               B, Bk, heads, Nq, Nk, C // heads, scale, _stream()), "skp_flash_attn_bwd_f32")
+        _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), C)
         if Bk == 1 and B > 1:
             dk, dv = dk.sum(dim=0, keepdim=True), dv.sum(dim=0, keepdim=True)
         return dq, dk, dv, None, None
@@ -906,97 +962,70 @@ def conv3x3_supported(x_shape, w_shape, need_grad=True):
     return max(ci * h * w, co * h * w, 16 * ci * co) * 4 < 2 ** 31
 
 
+# transformed-filter forms of a 3x3 weight: (C entry, floats per channel pair)
+_FILTER_FORMS = {"f2": ("skp_conv3x3_filter_f32", 16),          # Winograd F(2x2,3x3)
+                 "f4": ("skp_conv3x3_f4_filter_f32", 36),       # Winograd F(4x4,3x3)
+                 "f4r": ("skp_conv3x3_f4r_filter_f32", 9),      # raw-filter form: the 9 taps in MFMA operand order
+                 "s2": ("skp_conv3x3_s2_filter_f32", 9)}        # stride-2 direct kernel
+
+
+def _filters(weight, form, backward=False):
+    """Filter of a frozen weight in the layout of one kernel form (`_FILTER_FORMS`), channel roles swapped for the
+    backward-data launch; built once per weight version and kept on the weight."""
+    def build():
+        w = _dev(weight.detach(), "weight")
+        co, ci = w.shape[:2]
+        name, per_pair = _FILTER_FORMS[form]
+        U = torch.empty(per_pair * co * ci, device=w.device, dtype=torch.float32)
+        if form == "s2":
+            N.check(N.lib().skp_conv3x3_s2_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, _stream()), name)
+        else:
+            N.check(getattr(N.lib(), name)(w.data_ptr(), U.data_ptr(), *((ci, co, 1) if backward else (co, ci, 0)), _stream()), name)
+        return U
+    return cached(weight, ("filters", form, bool(backward)), (weight,), build)
+
+
+# entries of bench.py, the tools and the kernel tests
 def _wino_filters(weight, backward):
-    """Transformed filter of a frozen weight, built once per (weight storage, version) and kept resident."""
-    key = "_skp_wino_bwd" if backward else "_skp_wino_fwd"
-    hit = getattr(weight, key, None)
-    tag = (weight._version, weight.data_ptr())       # data_ptr: `weight.data = ...` / load_state_dict(assign=True)
-    if hit is not None and hit[0] == tag and hit[1].device == weight.device:
-        return hit[1]
-    w = _dev(weight.detach(), "weight")
-    co, ci = w.shape[:2]
-    U = torch.empty(16 * co * ci, device=w.device, dtype=torch.float32)
-    if backward:
-        N.check(N.lib().skp_conv3x3_filter_f32(w.data_ptr(), U.data_ptr(), ci, co, 1, _stream()), "skp_conv3x3_filter_f32")
-    else:
-        N.check(N.lib().skp_conv3x3_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, 0, _stream()), "skp_conv3x3_filter_f32")
-    setattr(weight, key, (tag, U))
-    return U
+    return _filters(weight, "f2", backward)
+
+
+def _wino4_filters(weight, backward):
+    return _filters(weight, "f4", backward)
+
+
+def _wino4r_filters(weight, backward):
+    return _filters(weight, "f4r", backward)
 
 
 def _conv3x3_raw(x, U, bias, cout, variant=0, split=True, residual=None, out=None):
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
-    nbytes = N.lib().skp_conv3x3_workspace(B, ci, cout, H, W, int(variant)) if split else 0
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
-    N.check(N.lib().skp_conv3x3_f32(x.data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                    residual.data_ptr() if residual is not None else None, y.data_ptr(),
-                                    ws.data_ptr() if ws is not None else None, B, ci, cout, H, W, int(variant), _stream()),
-            "skp_conv3x3_f32")
+    ws = _workspace("skp_conv3x3_workspace", B, ci, cout, H, W, int(variant), device=x.device) if split else None
+    N.check(N.lib().skp_conv3x3_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
+                                    B, ci, cout, H, W, int(variant), _stream()), "skp_conv3x3_f32")
     return y
-
-
-def _wino4_filters(weight, backward):
-    """F(4x4,3x3) transformed filter of a frozen weight (36*Cin*Cout floats), built once and kept resident."""
-    key = "_skp_wino4_bwd" if backward else "_skp_wino4_fwd"
-    hit = getattr(weight, key, None)
-    tag = (weight._version, weight.data_ptr())
-    if hit is not None and hit[0] == tag and hit[1].device == weight.device:
-        return hit[1]
-    w = _dev(weight.detach(), "weight")
-    co, ci = w.shape[:2]
-    U = torch.empty(36 * co * ci, device=w.device, dtype=torch.float32)
-    if backward:
-        N.check(N.lib().skp_conv3x3_f4_filter_f32(w.data_ptr(), U.data_ptr(), ci, co, 1, _stream()), "skp_conv3x3_f4_filter_f32")
-    else:
-        N.check(N.lib().skp_conv3x3_f4_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, 0, _stream()), "skp_conv3x3_f4_filter_f32")
-    setattr(weight, key, (tag, U))
-    return U
 
 
 def _conv3x3_f4_raw(x, U, bias, cout, split=True, residual=None, out=None, stats=None):
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     if stats is not None:                            # unsplit launch that also leaves the output's block sums behind
-        N.check(N.lib().skp_conv3x3_f4_stats_f32(x.data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                 residual.data_ptr() if residual is not None else None, y.data_ptr(),
+        N.check(N.lib().skp_conv3x3_f4_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(),
                                                  stats.data_ptr(), B, ci, cout, H, W, _stream()), "skp_conv3x3_f4_stats_f32")
         return y
-    nbytes = N.lib().skp_conv3x3_f4_workspace(B, ci, cout, H, W) if split else 0
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
-    N.check(N.lib().skp_conv3x3_f4_f32(x.data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                       residual.data_ptr() if residual is not None else None, y.data_ptr(),
-                                       ws.data_ptr() if ws is not None else None, B, ci, cout, H, W, _stream()),
-            "skp_conv3x3_f4_f32")
+    ws = _workspace("skp_conv3x3_f4_workspace", B, ci, cout, H, W, device=x.device) if split else None
+    N.check(N.lib().skp_conv3x3_f4_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
+                                       B, ci, cout, H, W, _stream()), "skp_conv3x3_f4_f32")
     return y
-
-
-def _wino4r_filters(weight, backward):
-    """The 9 taps of a frozen weight in MFMA operand order for the raw-filter form (9*Cin*Cout floats), built once."""
-    key = "_skp_wino4r_bwd" if backward else "_skp_wino4r_fwd"
-    hit = getattr(weight, key, None)
-    tag = (weight._version, weight.data_ptr())
-    if hit is not None and hit[0] == tag and hit[1].device == weight.device:
-        return hit[1]
-    w = _dev(weight.detach(), "weight")
-    co, ci = w.shape[:2]
-    R = torch.empty(9 * co * ci, device=w.device, dtype=torch.float32)
-    if backward:
-        N.check(N.lib().skp_conv3x3_f4r_filter_f32(w.data_ptr(), R.data_ptr(), ci, co, 1, _stream()), "skp_conv3x3_f4r_filter_f32")
-    else:
-        N.check(N.lib().skp_conv3x3_f4r_filter_f32(w.data_ptr(), R.data_ptr(), co, ci, 0, _stream()), "skp_conv3x3_f4r_filter_f32")
-    setattr(weight, key, (tag, R))
-    return R
 
 
 def _conv3x3_f4r_raw(x, R, bias, cout, residual=None, out=None):
     """Small-spatial form (csrc/skp_conv_wino4.hip, skp_wino4r_*): raw taps + in-lane filter transform, input transform in the workspace."""
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
-    nbytes = N.lib().skp_conv3x3_f4r_workspace(B, ci, cout, H, W)
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    N.check(N.lib().skp_conv3x3_f4r_f32(x.data_ptr(), R.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                        residual.data_ptr() if residual is not None else None, y.data_ptr(), ws.data_ptr(),
+    ws = _workspace("skp_conv3x3_f4r_workspace", B, ci, cout, H, W, device=x.device)
+    N.check(N.lib().skp_conv3x3_f4r_f32(x.data_ptr(), R.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
                                         B, ci, cout, H, W, _stream()), "skp_conv3x3_f4r_f32")
     return y
 
@@ -1043,16 +1072,20 @@ def conv3x3_stats_blocks(x_shape, w_shape) -> int:
     return int(N.lib().skp_conv3x3_f4_stats_blocks(b, ci, co, h, w))
 
 
+def _rows_per_launch(ci, co, H, W) -> int:
+    """Batch rows one convolution launch takes under the kernels' 32-bit byte offsets (< 2 GiB per tensor)."""
+    return max(1, (2 ** 31 - 1) // (max(ci, co) * H * W * 4))
+
+
 def _conv3x3_run(x, weight, backward, bias, residual, cout, stats=None):
     w_shape = (weight.shape[1], weight.shape[0], 3, 3) if backward else weight.shape
     f4 = conv3x3_f4_ok(x.shape, w_shape)
     B, ci, H, W = x.shape
     if f4 and stats is None and conv3x3_f4r_ok(x.shape, cout):          # small spatial size, many channels: raw-filter form
-        return _conv3x3_f4r_raw(x, _wino4r_filters(weight, backward), bias, cout, residual=residual)
-    U = _wino4_filters(weight, backward) if f4 else _wino_filters(weight, backward)
+        return _conv3x3_f4r_raw(x, _filters(weight, "f4r", backward), bias, cout, residual=residual)
+    U = _filters(weight, "f4" if f4 else "f2", backward)
     run = _conv3x3_f4_raw if f4 else _conv3x3_raw
-    per_image = max(ci, cout) * H * W * 4
-    chunk = max(1, (2 ** 31 - 1) // per_image)           # rows per launch under the kernels' 2 GiB addressing limit
+    chunk = _rows_per_launch(ci, cout, H, W)
     if stats is not None:
         return _conv3x3_f4_raw(x, U, bias, cout, residual=residual, stats=stats)
     if B <= chunk:
@@ -1147,8 +1180,7 @@ def conv3x3_gn_fold_ok(x, norm: torch.nn.GroupNorm, weight, *others) -> bool:
         return False
     B, ci, H, W = x.shape
     co = int(weight.shape[0])
-    chunk = max(1, (2 ** 31 - 1) // (max(ci, co) * H * W * 4))            # the launch shape the batch chunks will have
-    rows = min(B, chunk)
+    rows = min(B, _rows_per_launch(ci, co, H, W))                        # the launch shape the batch chunks will have
     return bool(N.lib().skp_conv3x3_f4_gn_ok(rows, ci, co, H, W)) and (B % rows == 0 or bool(
         N.lib().skp_conv3x3_f4_gn_ok(B % rows, ci, co, H, W)))
 
@@ -1168,9 +1200,7 @@ def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, re
     mean = torch.empty(B, G, device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
     coef = torch.empty(B, C, 2, device=x.device, dtype=torch.float32)
-    blocks = getattr(x, "_skp_blocks", None) if GN_FUSED_STATS else None
-    if blocks is not None and (blocks[0].shape[0] != B or blocks[0].shape[1] != C or blocks[1] * blocks[2] != H * W):
-        blocks = None
+    blocks = _blocks(x)
     lib, st = N.lib(), _stream()
     if blocks is not None:
         bs, nblk, pix = blocks
@@ -1184,11 +1214,11 @@ def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, re
                                             norm.weight.data_ptr(), norm.bias.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                             coef.data_ptr(), None, 0, 0, ws.data_ptr(), B, C, G, H * W, float(norm.eps), st),
                 "skp_group_norm_coef_f32")
-    U = _wino4_filters(weight, False)
+    U = _filters(weight, "f4")
     y = torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     nblk = conv3x3_stats_blocks(x.shape, weight.shape) if (want_stats and _stats_useful(cout, H, W)) else 0
     stats = torch.empty(B, cout, nblk, 2, device=x.device, dtype=torch.float32) if nblk else None
-    chunk = max(1, (2 ** 31 - 1) // (max(C, cout) * H * W * 4))          # rows per launch under the kernels' 2 GiB addressing limit
+    chunk = _rows_per_launch(C, cout, H, W)
     for b0 in range(0, B, chunk):
         b1 = min(B, b0 + chunk)
         N.check(lib.skp_conv3x3_f4_gn_f32(x[b0:b1].data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
@@ -1232,29 +1262,15 @@ def mfma_issue_rate(waves_per_simd: int = 1, iters: int = 20000, device=None) ->
     return float(out.value)
 
 
-_QKV_CACHE = {}
-
-
 def _qkv_stack(wq, wk, wv):
     """[3, C, C] stack of the three frozen projection weights of a self-attention block (made once per block)."""
     return weight_stack([wq, wk, wv])
 
 
 def weight_stack(ws):
-    """[len(ws), N, K] stack of frozen [N, K] weights (~200 MB over SD-1.5's attention projections), one entry per list of
-    parameters: keyed by the identity of the first one, re-made -- in place of the old entry, which is thereby released -- whenever
-    a parameter's storage or version has moved (`.to()`, dtype change, `load_state_dict`), dropped with its model."""
-    import weakref
-    key = (id(ws[0]), len(ws))
-    tag = tuple((w._version, w.data_ptr(), w.device, w.dtype) for w in ws)
-    hit = _QKV_CACHE.get(key)
-    if hit is not None and hit[0] == tag and hit[2]() is ws[0]:
-        return hit[1]
-    w3 = torch.stack([w.detach() for w in ws]).contiguous()
-    for dead in [k_ for k_, v_ in _QKV_CACHE.items() if v_[2]() is None]:     # stacks of models that are gone
-        del _QKV_CACHE[dead]
-    _QKV_CACHE[key] = (tag, w3, weakref.ref(ws[0]))
-    return w3
+    """[len(ws), N, K] stack of frozen [N, K] weights (~200 MB over SD-1.5's attention projections), kept on the first one per
+    list of members and re-made whenever a member's storage or version has moved (`.to()`, dtype change, `load_state_dict`)."""
+    return cached(ws[0], ("stack", *map(id, ws)), ws, lambda: torch.stack([w.detach() for w in ws]).contiguous())
 
 
 QKV_STACKED = True   # one batched GEMM with a broadcast A operand
@@ -1322,11 +1338,7 @@ class SelfAttnQKVFn(torch.autograd.Function):
         B, Nq, C = q.shape
         out = torch.empty_like(q)
         lse = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
-        if FLASH_SPLIT and flash_split_ok(B, B, heads, Nq, Nq, C // heads):
-            _flash_fwd_split(q, k, v, out, lse, heads, float(scale))
-        else:
-            N.check(N.lib().skp_flash_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                                   B, B, heads, Nq, Nq, C // heads, float(scale), _stream()), "skp_flash_attn_fwd_f32")
+        _flash_fwd(q, k, v, out, lse, heads, scale)
         ctx.save_for_backward(q, k, v, out, lse, wq, wk, wv)
         ctx.meta = (int(heads), float(scale), tuple(x.shape))
         return out
@@ -1339,21 +1351,7 @@ class SelfAttnQKVFn(torch.autograd.Function):
         B, Nq, C = q.shape
         d3 = torch.empty(B * Nq, 3 * C, device=q.device, dtype=torch.float32)
         p = d3.data_ptr()
-        if FLASH_SPLIT and Nq >= FLASH_SPLIT_MIN_KEYS and N.lib().skp_flash_attn_bwd_split_ok(B, B, heads, Nq, Nq, C // heads):
-            nbytes = N.lib().skp_flash_attn_bwd_split_workspace(B, B, heads, Nq, Nq, C // heads)
-            ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-            N.check(N.lib().skp_flash_attn_bwd_split_ld_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                                            lse.data_ptr(), p, p + 4 * C, p + 8 * C, ws.data_ptr(), B, B, heads, Nq, Nq,
-                                                            C // heads, scale, 3 * C, _stream()), "skp_flash_attn_bwd_split_ld_f32")
-            dx = torch.mm(d3, _qkv_stack(wq, wk, wv).view(3 * C, wq.shape[1]))
-            return dx.view(xshape), None, None, None, None, None
-        nbytes = N.lib().skp_flash_attn_bwd_workspace(B, B, heads, Nq, Nq, C // heads)
-        if nbytes < 0:
-            N.check(int(nbytes), "skp_flash_attn_bwd_workspace")
-        ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
-        N.check(N.lib().skp_flash_attn_bwd_ld_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                                  lse.data_ptr(), p, p + 4 * C, p + 8 * C, ws.data_ptr(), B, B, heads, Nq, Nq,
-                                                  C // heads, scale, 3 * C, _stream()), "skp_flash_attn_bwd_ld_f32")
+        _flash_bwd(q, k, v, out, dout, lse, heads, scale, p, p + 4 * C, p + 8 * C, 3 * C)
         dx = torch.mm(d3, _qkv_stack(wq, wk, wv).view(3 * C, wq.shape[1]))
         return dx.view(xshape), None, None, None, None, None
 
@@ -1441,33 +1439,20 @@ def conv3x3_s2(x, weight, bias=None, pad: int = 0, want_stats: bool = False):
 
 def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
     x = _dev(x.detach(), "x")
-    key = "_skp_s2"
-    hit = getattr(weight, key, None)
-    tag = (weight._version, weight.data_ptr())
-    if hit is not None and hit[0] == tag and hit[1].device == weight.device:
-        U = hit[1]
-    else:
-        w = _dev(weight.detach(), "weight")
-        U = torch.empty(9 * w.shape[0] * w.shape[1], device=w.device, dtype=torch.float32)
-        N.check(N.lib().skp_conv3x3_s2_filter_f32(w.data_ptr(), U.data_ptr(), w.shape[0], w.shape[1], _stream()),
-                "skp_conv3x3_s2_filter_f32")
-        setattr(weight, key, (tag, U))
+    U = _filters(weight, "s2")
     B, ci, H, W = x.shape
     co = weight.shape[0]
     y = torch.empty(B, co, H // 2, W // 2, device=x.device, dtype=torch.float32)
     if want_stats and GN_FUSED_STATS:
         nblk = (H // 16) * (W // 32)
         stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
-        N.check(N.lib().skp_conv3x3_s2_stats_f32(x.data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                 y.data_ptr(), stats.data_ptr(), B, ci, co, H, W, int(pad), _stream()),
-                "skp_conv3x3_s2_stats_f32")
+        N.check(N.lib().skp_conv3x3_s2_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), stats.data_ptr(),
+                                                 B, ci, co, H, W, int(pad), _stream()), "skp_conv3x3_s2_stats_f32")
         y._skp_blocks = (stats, nblk, 128)
         return y
-    nbytes = N.lib().skp_conv3x3_s2_workspace(B, ci, co, H, W)    # > 0: small grid, K split over the input channels
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes > 0 else None
-    N.check(N.lib().skp_conv3x3_s2_ws_f32(x.data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                          ws.data_ptr() if ws is not None else None, B, ci, co, H, W, int(pad), _stream()),
-            "skp_conv3x3_s2_ws_f32")
+    ws = _workspace("skp_conv3x3_s2_workspace", B, ci, co, H, W, device=x.device)    # small grid: K split over the input channels
+    N.check(N.lib().skp_conv3x3_s2_ws_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(ws), B, ci, co, H, W,
+                                          int(pad), _stream()), "skp_conv3x3_s2_ws_f32")
     return y
 
 

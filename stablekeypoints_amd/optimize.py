@@ -332,9 +332,11 @@ class GraphedStep:
             self.context.grad = torch.zeros_like(self.context)    # the captured backward ACCUMULATES into this tensor
         st["grad"] = self.context.grad
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        # kept values of the frozen weights (filters, stacks, offsets, the time embedding) that the graph reads: held with it, so an
+        # eager step of another group size that replaces them in its caches cannot free them under the replays
+        with ops.recording() as held, torch.cuda.graph(graph):
             self._body(st)
-        st["graph"] = graph
+        st["graph"], st["held"] = graph, held
 
     def _stage(self, st, images, thetas, noise):
         n = st["n"]

@@ -575,26 +575,90 @@ def test_group_indices_order_is_loader_independent(tmp_path):
     assert all(torch.equal(im, torch.stack([ds[i]["img"] for i in idx])) for _, idx, im in got)
 
 
-def test_weight_stack_is_cached_per_parameter_list_and_follows_versions():
+def test_weight_stack_is_kept_per_member_list_and_follows_versions():
     """Stacked copies of frozen projection weights (q | k | v of a self-attention block, k / v of the cross-attention layers of one
-    width): made once, re-made when a parameter is written, dropped when its model is gone."""
+    width): made once per list of members, re-made in place of the old entry when a member is written, dropped with the model."""
     import gc
-    import torch
+    import weakref
     from stablekeypoints_amd import ops
-    a, b = torch.nn.Parameter(torch.randn(4, 3)), torch.nn.Parameter(torch.randn(4, 3))
+    a, b, c = (torch.nn.Parameter(torch.randn(4, 3), requires_grad=False) for _ in range(3))
     s1 = ops.weight_stack([a, b])
     assert s1.shape == (2, 4, 3) and torch.equal(s1[1], b.detach())
     assert ops.weight_stack([a, b]) is s1
+    s_ac = ops.weight_stack([a, c])                               # same first member and length, another list: its own entry
+    assert torch.equal(s_ac[1], c.detach()) and ops.weight_stack([a, b]) is s1 and ops.weight_stack([a, c]) is s_ac
+    gone = weakref.ref(s1)
     with torch.no_grad():
         b.mul_(2.0)                                               # version bump: the stack must follow
     s2 = ops.weight_stack([a, b])
     assert s2 is not s1 and torch.equal(s2[1], b.detach())
-    n = len(ops._QKV_CACHE)
-    b.data = b.data.clone()                                       # storage moved (`.to()`, dtype change): the entry is REPLACED, not added
+    del s1
+    assert gone() is None                                         # the old stack was released, not kept beside the new one
+    gone = weakref.ref(s2)
+    b.data = b.data.clone()                                       # storage moved (`.to()`, dtype change): the entry is REPLACED
     s3 = ops.weight_stack([a, b])
-    assert s3 is not s2 and len(ops._QKV_CACHE) == n
-    del a, b, s1, s2, s3
+    assert s3 is not s2 and torch.equal(s3, s2)
+    del s2
+    assert gone() is None
+    gone = weakref.ref(s3)
+    del a, b, c, s3, s_ac
     gc.collect()
-    c = torch.nn.Parameter(torch.randn(2, 2))
-    ops.weight_stack([c, c])                                      # inserting prunes entries whose owner is gone
-    assert len(ops._QKV_CACHE) <= n
+    assert gone() is None                                         # entries die with their owner
+
+
+def test_norm2_offset_is_kept_per_row_count_and_its_time_embedding_matched_by_identity():
+    """`fused._norm2_offset` on the frozen-value cache: one entry per row count, so groups of 2 and 1 images do not evict each
+    other's offsets (a captured step reads them on every replay); the time embedding, not a parameter, is matched by identity --
+    an equal tensor that is another object rebuilds the entry in place; one that takes gradients keeps nothing."""
+    import weakref
+    from stablekeypoints_amd.ldm.fused import _norm2_offset
+    from stablekeypoints_amd.ldm.unet import ResnetBlock2D
+    res = ResnetBlock2D(8, 16, temb_ch=4, groups=4).requires_grad_(False)
+    t2, t1 = torch.randn(2, 4), torch.randn(1, 4)
+    o2, o1 = _norm2_offset(res, 2, t2), _norm2_offset(res, 1, t1)
+    assert _norm2_offset(res, 2, t2) is o2 and _norm2_offset(res, 1, t1) is o1
+    assert torch.equal(o2, res.conv1.bias[None] + res.time_emb_proj(torch.nn.functional.silu(t2)))
+    gone = weakref.ref(o2)
+    o2b = _norm2_offset(res, 2, t2.clone())
+    assert o2b is not o2 and torch.equal(o2b, o2)
+    del o2
+    assert gone() is None and _norm2_offset(res, 1, t1) is o1
+    tg = t2.clone().requires_grad_(True)
+    og = _norm2_offset(res, 2, tg)
+    assert og.requires_grad and _norm2_offset(res, 2, tg) is not og and _norm2_offset(res, 2, t2) is not og
+
+
+def test_frozen_value_cache_keeps_nothing_for_inputs_that_take_gradients_and_records_what_it_hands_out():
+    """`ops.cached`: an input that requires grad keeps no entry; inside `ops.recording()` (a graph capture) every value handed out
+    is held by the recording, so replacing the entry afterwards does not free what the graph reads."""
+    import weakref
+    from stablekeypoints_amd import ops
+    w = torch.nn.Parameter(torch.randn(3))
+    calls = []
+
+    def build():
+        calls.append(1)
+        return w.detach() * 2
+    assert ops.cached(w, "k", (w,), build) is not ops.cached(w, "k", (w,), build)
+    assert len(calls) == 2 and "_skp_cache" not in w.__dict__
+    w.requires_grad_(False)
+    with ops.recording() as held:
+        v = ops.cached(w, "k", (w,), build)
+        assert ops.cached(w, "k", (w,), build) is v and len(calls) == 3
+    assert any(h is v for h in held)
+    gone = weakref.ref(v)
+    with torch.no_grad():
+        w.add_(1.0)
+    v2 = ops.cached(w, "k", (w,), build)                          # outside the block: not recorded
+    del v
+    assert gone() is not None and not any(h is v2 for h in held)
+    del held
+    assert gone() is None
+
+
+def test_negative_workspace_query_raises_naming_the_query():
+    from stablekeypoints_amd import ops
+    with pytest.raises(RuntimeError, match="skp_flash_attn_bwd_workspace"):
+        ops._workspace("skp_flash_attn_bwd_workspace", 0, 0, 0, 0, 0, 0, device="cpu")
+    assert ops._workspace("skp_conv3x3_workspace", 0, 0, 0, 0, 0, 0, device="cpu") is None
+    assert ops._workspace("skp_flash_attn_bwd_workspace", 1, 1, 1, 1, 1, 7, device="cpu").numel() == 1

@@ -170,11 +170,44 @@ def test_graphed_step_replays_the_eager_step():
     assert g2.state[2] == "eager" and sum("stay on eager" in str(x.message) for x in w) == 1
 
 
-def test_vae_tail_composed_convolution_vs_module():
+def test_graphed_step_with_mixed_group_sizes_vs_eager():
+    """Groups of 2, 2, 2 (captured), 1 (eager), 2 (replay), 1, 2 images -- the tail groups of `images_per_forward` 2 at an odd
+    number of images per rank: the eager steps of the other group size must not free the kept values of the frozen weights (norm2
+    offsets per row count, time embeddings, filters, stacks) that the size-2 graph reads on every replay.  Every call against the
+    eager `group_step` on the same inputs, to the tolerances of the test above; the graphed step runs first, so a replay would
+    read whatever the eager step of the other size left in freed memory."""
+    from test_e2e_gpu import _setup
+    from stablekeypoints_amd.invertable_transform import RandomAffineWithInverse
+    from stablekeypoints_amd.optimize import GraphedStep, group_step
+    ldm, controllers, cpu, images, ctx, noise, args = _setup(R_up=128, T=16, n=2, size=512)
+    del cpu
+    dev, controller = next(iter(controllers.items()))
+    g = torch.Generator().manual_seed(6)
+    tr_a, tr_b = RandomAffineWithInverse(15, (0.8, 1.0), (0.25, 0.25)), RandomAffineWithInverse(15, (0.8, 1.0), (0.25, 0.25))
+    c_e = ctx.clone().cuda().requires_grad_(True)
+    c_g = ctx.clone().cuda().requires_grad_(True)
+    graphed = GraphedStep(ldm, c_g, args, controller, tr_b, denom=1, warmup=2)
+    for step, n in enumerate((2, 2, 2, 1, 2, 1, 2)):
+        img = torch.rand(n, 3, 512, 512, generator=g)
+        nz = torch.randn(2 * n, 4, 64, 64, generator=g).cuda()
+        th = torch.cat([R.affine_matrix(float(torch.rand(1, generator=g)) * 20 - 10, 0.85 + 0.1 * float(torch.rand(1, generator=g)),
+                                        (0.1, -0.05 * step)) for _ in range(n)])
+        lg = [v.clone() for v in graphed(img, noise=nz, thetas=th)]
+        le = group_step(ldm, img, c_e, args, controller, tr_a, denom=1, noise=nz, thetas=th)
+        for a_, b_ in zip(le, lg):
+            assert abs(a_.item() - b_.item()) <= 1e-5 * abs(a_.item()) + 1e-9, (step, n, a_.item(), b_.item())
+        assert_grad_close(c_g.grad, c_e.grad, f"graphed vs eager, step {step} ({n} images)", tol=1e-5)
+    st2, st1 = graphed.state[2], graphed.state[1]
+    assert st2 != "eager" and st2["graph"] is not None and st2["calls"] == 2, "the last three groups of 2 must have been replays"
+    assert st1 != "eager" and st1.get("graph") is None and st1["calls"] == 2
+
+
+def test_vae_tail_composed_convolution_is_kept_and_matches_the_module():
     """`AutoencoderKL.encode` on the fused path: `quant_conv(conv_out(silu(GroupNorm(h))))` as ONE Winograd convolution with the
     composed, zero-padded filter (ldm/fused.py: _vae_encode) against the module's own forward in fp64 on the same weights: posterior
     mean and log-variance; the composition follows the weights' versions."""
     import copy
+    from stablekeypoints_amd import ops
     from stablekeypoints_amd.ldm.fused import fuse_norms
     from stablekeypoints_amd.ldm.vae import AutoencoderKL
     torch.manual_seed(3)
@@ -188,8 +221,10 @@ def test_vae_tail_composed_convolution_vs_module():
     x = torch.rand(2, 3, 128, 128) * 2 - 1
     with torch.no_grad():
         want = ref.double().encode(x.double())["latent_dist"]
-        got = gpu.encode(x.cuda())["latent_dist"]
-        assert "_skp_tail" in gpu.__dict__, "the composed tail was not taken"
+        with ops.recording() as held:
+            got = gpu.encode(x.cuda())["latent_dist"]
+        tail = gpu.__dict__.get("_skp_cache", {}).get("vae_tail")
+        assert tail is not None and any(h is tail[2] for h in held), "the composed tail was not taken"
         for a, b in ((got.mean, want.mean), (got.logvar, want.logvar)):
             torch.testing.assert_close(a.double().cpu(), b, rtol=1e-4, atol=2e-5 * b.abs().max().item())
         gpu.quant_conv.bias.add_(1.0)                                        # version bump: the composition must follow
