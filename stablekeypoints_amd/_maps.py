@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from . import routes
 
 
 class FusedAttn:
@@ -63,6 +64,7 @@ class FusedAttn:
             if q.is_cuda:
                 self._mat = ops.materialize_probs(q, k, self.heads, self.scale, self.R)
             else:
+                routes.note("map.fwd", "host")
                 self._mat = _materialize_host(q, k, self.heads, self.scale, self.R)
         return self._mat
 
@@ -163,6 +165,7 @@ def collect_maps(controller, from_where=["up_cross"], upsample_res=512, layers=[
     else:
         # materialised entries (AttentionStore(materialize=True) or a foreign controller): the reference's
         # op sequence on device tensors
+        routes.note("map.collect", "reference_ops" if chosen[0].is_cuda else "host")
         per_layer = []
         for data in chosen:
             if isinstance(data, FusedAttn):

@@ -6,6 +6,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from . import routes as _routes
 
 
 def _points(flat: torch.Tensor, w: int) -> torch.Tensor:
@@ -51,13 +52,12 @@ def pixel_from_weighted_avg(heatmaps, distance=5):
     return torch.stack([torch.sum(x * norm, dim=[1, 2]), torch.sum(y * norm, dim=[1, 2])], dim=-1) + 0.5
 
 
-@torch.no_grad()
 def run_image_with_context_augmented(ldm, image, context, indices, device="cuda",
                                      from_where=["down_cross", "mid_cross", "up_cross"], layers=[0, 1, 2, 3, 4, 5],
                                      augmentation_iterations=20, noise_level=-1, augment_degrees=30,
                                      augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1), visualize=False,
                                      controllers=None, num_gpus=1, save_folder="outputs", upscale_size=512,
-                                     thetas=None, noise=None, shard_over_ranks=False):
+                                     thetas=None, noise=None, shard_over_ranks=False, routes="off"):
     """eval.py:197-355: maps of the selected tokens averaged over random affine views of ONE image.
 
     Reference loop: per augmentation -> UNet forward -> collect_maps(indices, upsample_res=upscale_size) ->
@@ -72,7 +72,23 @@ def run_image_with_context_augmented(ldm, image, context, indices, device="cuda"
     them, rank r takes views r, r+world, ... and the un-warped sum and the coverage count ([K,S,S] each) are
     all-reduced before the division, so the ensemble is the same `n` views as on one GPU and every rank returns the
     same averaged maps; a view count that does not divide by the world size raises.
-    `thetas` [n,2,3] / `noise` [n,4,h,w] inject the draws for ALL n views (parity tests)."""
+    `thetas` [n,2,3] / `noise` [n,4,h,w] inject the draws for ALL n views (parity tests).
+    `routes`: "off" | "report" | "strict" -- the route ledger's rule for this call (`routes.guard`): "report" resets the ledger
+    first, so that `routes.table()` afterwards describes this call; "strict" also raises `routes.UnexpectedRoute` at the gate that
+    leaves the HIP kernels for a route outside `routes.DOCUMENTED_LIBRARY_ROUTES`."""
+    with _routes.guard(routes):
+        return _run_image_with_context_augmented(ldm, image, context, indices, device, from_where, layers, augmentation_iterations, noise_level, augment_degrees, augment_scale,
+                                                 augment_translate, visualize, controllers, num_gpus, save_folder, upscale_size, thetas, noise,
+                                                 shard_over_ranks)
+
+
+@torch.no_grad()
+def _run_image_with_context_augmented(ldm, image, context, indices, device="cuda",
+                                     from_where=["down_cross", "mid_cross", "up_cross"], layers=[0, 1, 2, 3, 4, 5],
+                                     augmentation_iterations=20, noise_level=-1, augment_degrees=30,
+                                     augment_scale=(0.9, 1.1), augment_translate=(0.1, 0.1), visualize=False,
+                                     controllers=None, num_gpus=1, save_folder="outputs", upscale_size=512,
+                                     thetas=None, noise=None, shard_over_ranks=False):
     import numpy as np
     from . import dist as skp_dist
     from .invertable_transform import RandomAffineWithInverse

@@ -8,6 +8,7 @@ import torch
 
 from . import dist as skp_dist
 from . import ops, ptp_utils
+from . import routes as _routes
 from ._maps import collect_maps_batched
 from .eval import find_max_pixel, pixel_from_weighted_avg, run_images_with_context_augmented
 from .optimize import build_dataset, token_order
@@ -74,9 +75,8 @@ def keypoints_from_maps(attention_maps, max_loc_strategy="argmax"):
     return pixel_from_weighted_avg(attention_maps) / size
 
 
-@torch.no_grad()
 def precompute_all_keypoints(ldm, context, top_indices, args, controllers, num_gpus,
-                             from_where=["down_cross", "mid_cross", "up_cross"], dataset=None, draws=None):
+                             from_where=["down_cross", "mid_cross", "up_cross"], dataset=None, draws=None, routes="off"):
     """keypoint_regressor.py:111-198 -> (source_keypoints [N,K,2], target_keypoints [N,...] or None, visibility or None)
     for the first `min(len(dataset), args.max_num_points)` images of a shuffled pass (:155-165).
 
@@ -88,7 +88,17 @@ def precompute_all_keypoints(ldm, context, top_indices, args, controllers, num_g
     items, once: pixels and annotations together), every rank returns all of them in order.
     `dataset`: any `{"img"[, "kpts", "visibility"]}` dataset (default: `build_dataset(args)`; `synthetic` / `custom` have no
     annotations => targets None).  `draws = (order [N], noise [N*n,4,h,w], thetas [N*n,2,3])` injects the loader order
-    and the per-view draws in the reference's draw order (parity tests; the reference takes them from the global RNGs)."""
+    and the per-view draws in the reference's draw order (parity tests; the reference takes them from the global RNGs).
+    `routes`: "off" | "report" | "strict" -- the route ledger's rule for this call (`routes.guard`): "report" resets the ledger
+    first, so that `routes.table()` afterwards describes this call; "strict" also raises `routes.UnexpectedRoute` at the gate that
+    leaves the HIP kernels for a route outside `routes.DOCUMENTED_LIBRARY_ROUTES`."""
+    with _routes.guard(routes):
+        return _precompute_all_keypoints(ldm, context, top_indices, args, controllers, num_gpus, from_where, dataset, draws)
+
+
+@torch.no_grad()
+def _precompute_all_keypoints(ldm, context, top_indices, args, controllers, num_gpus,
+                             from_where=["down_cross", "mid_cross", "up_cross"], dataset=None, draws=None):
     world, rank = skp_dist.world_size(), skp_dist.rank()
     dev, controller = next(iter(controllers.items()))
     if dataset is None:

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from .. import routes
 from .attention import AttentionBlock, BasicTransformerBlock, Transformer2DModel
 from .unet import Downsample2D, ResnetBlock2D, UNet2DConditionModel
 
@@ -22,7 +23,9 @@ def _resnet_forward(m: ResnetBlock2D):
 
     def forward(x, temb=None):
         if not ops.group_norm_supported(x, m.norm1.num_groups):
+            routes.note("resnet", "eager")
             return orig(x, temb)
+        routes.note("resnet", "fused")
         # where the convolution runs with one output-channel group and no autograd (the VAE's first level: 128 -> 128 at the
         # image resolution, 1 GB activations) the norm is applied inside the convolution's patch load: no apply pass
         if ops.conv3x3_gn_fold_ok(x, m.norm1, m.conv1.weight):
@@ -69,6 +72,7 @@ def _time_path(m: UNet2DConditionModel):
         host = not torch.is_tensor(timestep) or (timestep.device.type == "cpu" and timestep.numel() <= 64)
         tag = ops.frozen_tag([*m.time_embedding.parameters(), *(m.add_embedding.parameters() if m.add_embedding is not None else ())])
         if not host or tag is None or added_cond_kwargs is not None:
+            routes.note("time_embedding", "eager")
             return orig(sample, timestep, added_cond_kwargs)
         vals = tuple(float(v) for v in (timestep.reshape(-1).tolist() if torch.is_tensor(timestep) else [timestep]))
         key = (vals, int(sample.shape[0]), tuple(sample.shape[-2:]), sample.device, sample.dtype, tag)
@@ -97,9 +101,12 @@ def _transformer_forward(m: Transformer2DModel):
 
     def forward(x, context=None):
         if not ops.group_norm_supported(x, m.norm.num_groups):
+            routes.note("transformer2d", "eager")
             return orig(x, context)
         if not ops.layout_supported(x):
+            routes.note("transformer2d", "eager")
             return orig(x, context)                  # the module's own forward knows both projection layouts
+        routes.note("transformer2d", "fused")
         h, x = ops.group_norm_silu_fork(x, m.norm, silu=False)          # x' = x for the residual add at the end
         # token layout throughout: the 1x1 convolutions are nn.Linear over tokens (bias fused in the GEMM), the two
         # permutes are tiled transposes and the residual add rides on the way back
@@ -120,7 +127,9 @@ def _block_forward(m: BasicTransformerBlock):
     def forward(h, context=None):
         if not (ops.add_layer_norm_supported(h, m.norm1) and ops.add_layer_norm_supported(h, m.norm2)
                 and ops.add_layer_norm_supported(h, m.norm3)):
+            routes.note("transformer_block", "eager")
             return orig(h, context=context)
+        routes.note("transformer_block", "fused")
         h, n = ops.add_layer_norm(None, h, m.norm1)
         h, n = ops.add_layer_norm(m.attn1(n), h, m.norm2)
         h, n = ops.add_layer_norm(m.attn2(n, context=context), h, m.norm3)
@@ -135,7 +144,9 @@ def _vae_attention_forward(m: AttentionBlock):
 
     def forward(x):
         if not (ops.group_norm_supported(x, m.group_norm.num_groups) and ops.layout_supported(x)):
+            routes.note("vae.attention", "eager")
             return orig(x)
+        routes.note("vae.attention", "lib_core")
         b, c, hh, ww = x.shape
         t = ops.nchw_to_tokens(ops.group_norm_silu(x, m.group_norm, silu=False))        # [b, hh*ww, c]
         q, k, v = m.query(t), m.key(t), m.value(t)
@@ -167,7 +178,12 @@ def _downsample_forward(m):
     def forward(x):
         frozen = not (m.conv.weight.requires_grad or (m.conv.bias is not None and m.conv.bias.requires_grad))
         if frozen and m.conv.stride == (2, 2) and ops.conv3x3_s2_supported(x, m.conv.weight):
+            routes.note("downsample", "s2_direct")
             return ops.conv3x3_s2(x, m.conv.weight, m.conv.bias, pad=0 if m.padding == 0 else 1, want_stats=True)
+        # (a layer the kernel refuses for its 16 x 32 pixel tile ALONE is a site of its own, a documented route; any other refusal --
+        # unfrozen weights, stride, channels, CONV3X3_MODE -- is `downsample` / eager whatever the input's size)
+        tile_only = frozen and m.conv.stride == (2, 2) and ops.conv3x3_s2_tile_only(x, m.conv.weight)
+        routes.note("downsample.untiled" if tile_only else "downsample", "eager")
         return orig(x)
     return forward
 
@@ -202,13 +218,16 @@ def _vae_encode(m):
               and q.weight.shape[0] <= 32 and enc.conv_out.kernel_size == (3, 3) and enc.conv_out.padding == (1, 1)
               and q.bias is not None and enc.conv_out.bias is not None and not any(p.requires_grad for p in tail_params()))
         if not ok:
+            routes.note("vae.tail", "eager")
             return orig(x)
         h = enc.conv_in(x)
         for blk in enc.down_blocks:
             h = blk(h)
         h = enc.mid_block(h)
         if not (ops.group_norm_supported(h, enc.conv_norm_out.num_groups) and ops.conv3x3_wanted(h.shape, (32, h.shape[1], 3, 3))):
+            routes.note("vae.tail", "eager")
             return {"latent_dist": DiagonalGaussianDistribution(q(enc.conv_out(F.silu(enc.conv_norm_out(h)))))}
+        routes.note("vae.tail", "composed")
         wp, bp = ops.cached(m, "vae_tail", tail_params(), compose)
         h = ops.group_norm_silu(h, enc.conv_norm_out)
         y = ops.conv3x3_auto(h, wp, bp)

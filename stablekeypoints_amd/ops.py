@@ -13,6 +13,7 @@ from typing import List, Sequence, Tuple
 import torch
 
 from . import _native as N
+from . import routes
 
 
 def _stream() -> int:
@@ -153,6 +154,7 @@ def _map_fwd(S: Sequence[torch.Tensor], sides: Sequence[int], B: int, H: int, T:
     si, _k2 = N.int_array(sides)
     lib, st = N.lib(), _stream()
     if map_wide_supported(T, R, sides):
+        routes.note("map.fwd", "map_wide")
         M = torch.empty(B, n_rows if tokrow is not None else T, R, R, device=dev, dtype=torch.float32)
         lse = torch.empty(B, L * H, R * R, device=dev, dtype=torch.float32)
         sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
@@ -172,9 +174,11 @@ def _map_fwd(S: Sequence[torch.Tensor], sides: Sequence[int], B: int, H: int, T:
                                             ldt, T * R * R, mode, st), "skp_attn_map_fwd_ex_f32")
 
     if T <= TOKEN_GROUP:
+        routes.note("map.fwd", "map_fused")
         lse = torch.empty(B, L * H, R * R, device=dev, dtype=torch.float32)
         launch(0, T, 0, lse, None)
         return M, lse
+    routes.note("map.fwd", "map_groups")
     parts = []
     for t0, t1 in _groups(T):
         parts.append(torch.empty(B, L * H, R * R, device=dev, dtype=torch.float32))
@@ -200,8 +204,10 @@ def _map_bwd(S, dS, sides, B, H, T, R, dM, lse):
                                             ldt, T * R * R, mode, st), "skp_attn_map_bwd_ex_f32")
 
     if T <= TOKEN_GROUP:
+        routes.note("map.bwd", "map_dense")
         launch(0, T, 0, None)
         return
+    routes.note("map.bwd", "map_dense_groups")
     dots = []
     for t0, t1 in _groups(T):
         dots.append(torch.empty(B, L * H, R * R, device=dev, dtype=torch.float32))
@@ -250,8 +256,10 @@ def _map_bwd_sparse(S, sides, B, H, T, R, sel, G, lse):
     si, _k0 = N.int_array(sides)
     if MAP_BWD_MODE != "sweep" and T <= COL_MAX_T and map_bwd_col_supported(sides, K, R, T, H):
         query, name = "skp_attn_map_bwd_col_workspace", "skp_attn_map_bwd_col_f32"              # column sweep
+        routes.note("map.bwd", "map_col")
     else:
         query, name = "skp_attn_map_bwd_sparse_workspace", "skp_attn_map_bwd_sparse_f32"        # token-major sweep
+        routes.note("map.bwd", "map_tok")
     ws = _workspace(query, si, L, B, H, T, R, K, device=G.device)
     sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
     dp, _k2 = N.ptr_array([t.data_ptr() for t in dS])
@@ -516,6 +524,7 @@ class MapLossesFn(torch.autograd.Function):
         # (a caller-supplied score function is honoured: only the stock order of optimize.token_order is batched)
         batched = (strategy in ("gaussian", "entropy", "consistent") and T <= SELECT_MAX_TOKENS and n_cand <= SELECT_MAX_CANDIDATES
                    and K >= 2 and MAP_LOSSES_BATCHED and getattr(meta.get("score_fn"), "_skp_stock_order", False))
+        routes.note("map.select", "batched" if batched else "per_image")
         if batched:
             flat = M.reshape(B * T, R, R)
             st_all = token_stats(flat[:n * T], num_subjects=ns, sigma=sigma, want_kl=strategy == "gaussian",
@@ -613,6 +622,7 @@ class CrossAttnFn(torch.autograd.Function):
         Bk, T, _ = k.shape
         out = torch.empty_like(q)
         lse = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
+        routes.note("attn.cross", routes.cross_attn_form(B, heads, Nq, T, C // heads, N.lib().skp_tune_get(b"cross_attn_ts") == 1))
         N.check(N.lib().skp_cross_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                B, Bk, heads, Nq, T, C // heads, float(scale), _stream()),
                 "skp_cross_attn_fwd_f32")
@@ -642,6 +652,7 @@ class CrossAttnFn(torch.autograd.Function):
 
 def cross_attention(q, k, v, heads: int, scale: float):
     if k.shape[1] > CROSS_ATTN_MAX_T:
+        routes.note("attn.cross", "flash")
         return FlashAttnFn.apply(q, k, v, int(heads), float(scale))
     return CrossAttnFn.apply(q, k, v, int(heads), float(scale))
 
@@ -665,7 +676,9 @@ class GroupNormSiLUFn(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(Nn, groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
+        routes.note("group_norm", "gn_apply")
         if blocks is not None:                       # statistics from the producing convolution's epilogue
+            routes.note("group_norm.stats", "producer_blocks")
             bs, nblk, pix = blocks
             N.check(N.lib().skp_group_norm_fwd_blocks_f32(x.data_ptr(), off_c.data_ptr() if off_c is not None else None,
                                                           gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
@@ -673,6 +686,7 @@ class GroupNormSiLUFn(torch.autograd.Function):
                                                           Hh * Ww, float(eps), int(silu), _stream()),
                     "skp_group_norm_fwd_blocks_f32")
         else:
+            routes.note("group_norm.stats", "own_pass")
             ws = torch.empty(Nn * groups * 64 * 3, device=x.device, dtype=torch.float32)
             N.check(N.lib().skp_group_norm_fwd_f32(x.data_ptr(), off_c.data_ptr() if off_c is not None else None,
                                                    gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
@@ -787,10 +801,12 @@ def _flash_fwd(q, k, v, out, lse, heads, scale, split=None):
     if split is None:
         split = flash_split_ok(*shape)
     if split:
+        routes.note("flash.fwd", "flash_split")
         ws = _workspace("skp_flash_attn_fwd_split_workspace", *shape, device=q.device)
         N.check(N.lib().skp_flash_attn_fwd_split_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                      _ptr(ws), *shape, float(scale), _stream()), "skp_flash_attn_fwd_split_f32")
     else:
+        routes.note("flash.fwd", "flash_f32" if shape[5] in FA2_HEAD_DIMS else "self_attn_gen1")
         N.check(N.lib().skp_flash_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                *shape, float(scale), _stream()), "skp_flash_attn_fwd_f32")
 
@@ -805,8 +821,10 @@ def _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, ld, split=None
         split = flash_split_ok(*shape, backward=True)
     if split:
         query, name = "skp_flash_attn_bwd_split_workspace", "skp_flash_attn_bwd_split_ld_f32"
+        routes.note("flash.bwd", "flash_split")
     else:
         query, name = "skp_flash_attn_bwd_workspace", "skp_flash_attn_bwd_ld_f32"
+        routes.note("flash.bwd", "flash_f32" if shape[5] in FA2_HEAD_DIMS else "self_attn_gen1")
     ws = _workspace(query, *shape, device=q.device)
     N.check(getattr(N.lib(), name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
                                    dq, dk, dv, _ptr(ws), *shape, float(scale), int(ld), _stream()), name)
@@ -864,6 +882,7 @@ SelfAttnFn = FlashAttnFn
 
 
 def self_attention(q, k, v, heads: int, scale: float):
+    routes.note("attn.self", "plain")
     return FlashAttnFn.apply(q, k, v, int(heads), float(scale))
 
 
@@ -943,6 +962,7 @@ class AddLayerNormFn(torch.autograd.Function):
 
 def add_layer_norm(d, h, norm: torch.nn.LayerNorm):
     """Returns (d + h, norm(d + h)); d may be None -> (h, norm(h))."""
+    routes.note("add_layer_norm", "add_ln")
     return AddLayerNormFn.apply(d, h, norm.weight, norm.bias, norm.eps)
 
 
@@ -1081,11 +1101,14 @@ def _conv3x3_run(x, weight, backward, bias, residual, cout, stats=None):
     w_shape = (weight.shape[1], weight.shape[0], 3, 3) if backward else weight.shape
     f4 = conv3x3_f4_ok(x.shape, w_shape)
     B, ci, H, W = x.shape
+    site = "conv3x3.bwd_data" if backward else "conv3x3"
     if f4 and stats is None and conv3x3_f4r_ok(x.shape, cout):          # small spatial size, many channels: raw-filter form
+        routes.note(site, "wino4_raw")
         return _conv3x3_f4r_raw(x, _filters(weight, "f4r", backward), bias, cout, residual=residual)
     U = _filters(weight, "f4" if f4 else "f2", backward)
     run = _conv3x3_f4_raw if f4 else _conv3x3_raw
     chunk = _rows_per_launch(ci, cout, H, W)
+    routes.note(site, routes.wino4_form(cout, min(B, chunk), H, W) if f4 else "wino2")
     if stats is not None:
         return _conv3x3_f4_raw(x, U, bias, cout, residual=residual, stats=stats)
     if B <= chunk:
@@ -1118,6 +1141,7 @@ class Conv3x3Fn(torch.autograd.Function):
             if conv3x3_wanted(dy.shape, (ci, co, 3, 3)):
                 dx = _conv3x3_run(_dev(dy, "dy"), w, True, None, None, ci)
             else:       # too few tiles for these kernels: library backward-data
+                routes.note("conv3x3.bwd_data", "lib")
                 dx = torch.nn.grad.conv2d_input((dy.shape[0], ci, dy.shape[2], dy.shape[3]), w, dy, padding=1)
         return dx, None, None, (dy if ctx.needs_input_grad[3] else None), None
 
@@ -1154,6 +1178,7 @@ def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
     if (frozen and residual is None and x.is_cuda and x.dtype == torch.float32 and CONV3X3_MODE != "lib"
             and weight.shape[1] <= 4 and x.shape[3] % 2 == 0 and not (torch.is_grad_enabled() and x.requires_grad)):
         return conv3x3_small(x, weight, bias, want_stats=want_stats)   # conv_in layers: output-bandwidth bound, own VALU kernel
+    routes.note("conv_out" if weight.shape[0] <= 8 else "conv3x3", "lib")     # (<= 8 output channels = a conv_out, by the rule above)
     if residual is None:
         return torch.nn.functional.conv2d(x, weight, bias, padding=1)
     y = torch.nn.functional.conv2d(x, weight, None, padding=1)
@@ -1202,6 +1227,9 @@ def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, re
     coef = torch.empty(B, C, 2, device=x.device, dtype=torch.float32)
     blocks = _blocks(x)
     lib, st = N.lib(), _stream()
+    routes.note("group_norm", "gn_fold")
+    routes.note("conv3x3", "wino4_c128")             # (the only form skp_conv3x3_f4_gn_ok admits)
+    routes.note("group_norm.stats", "producer_blocks" if blocks is not None else "own_pass")
     if blocks is not None:
         bs, nblk, pix = blocks
         N.check(lib.skp_group_norm_coef_f32(None, off_c.data_ptr() if off_c is not None else None, norm.weight.data_ptr(),
@@ -1235,6 +1263,7 @@ def conv3x3_small(x, weight, bias=None, want_stats=False):
     kernel serves it (the VAE's 3 -> 128 at image resolution) the output carries its block statistics for the GroupNorm that
     follows (`y._skp_blocks`, consumed by group_norm_silu / conv3x3_gn_silu): no separate pass over the 1 GB activation."""
     x, w = _dev(x.detach(), "x"), _dev(weight.detach(), "weight")
+    routes.note("conv_in", "small")
     B, ci, H, W = x.shape
     y = torch.empty(B, w.shape[0], H, W, device=x.device, dtype=torch.float32)
     bb = _dev(bias.detach(), "bias") if bias is not None else None
@@ -1367,6 +1396,7 @@ def self_attention_block(x, wq, wk, wv, heads: int, scale: float):
     if (QKV_STACKED and QKV_ACCUM and x.is_cuda and x.dim() == 3 and frozen and x.requires_grad
             and torch.is_grad_enabled() and wq.shape == wk.shape == wv.shape and wq.shape[0] % heads == 0
             and (wq.shape[0] // heads) in FA2_HEAD_DIMS):
+        routes.note("attn.self", "fused_qkv")
         return SelfAttnQKVFn.apply(_dev(x, "x"), wq, wk, wv, int(heads), float(scale))
     q, k, v = qkv_proj(x, wq, wk, wv)
     return self_attention(q, k, v, heads, scale)
@@ -1390,6 +1420,15 @@ def conv3x3_s2_supported(x, weight) -> bool:
     co = int(weight.shape[0])
     return (CONV3X3_MODE != "lib" and int(weight.shape[1]) == ci and ci % 16 == 0 and co % 32 == 0 and h % 16 == 0
             and w % 32 == 0 and max(b * ci * h * w, b * co * (h // 2) * (w // 2), 9 * ci * co) * 4 < 2 ** 31)
+
+
+def conv3x3_s2_tile_only(x, weight) -> bool:
+    """The stride-2 kernel refuses this input for its 16 x 32 pixel tile alone: the same tensor grown to the next tile multiple
+    would pass `conv3x3_s2_supported` (asked of a stride-0 view of that size: the gate reads shape, device and dtype only)."""
+    if x.dim() != 4 or 0 in x.shape:
+        return False
+    h, w = -(-x.shape[2] // 16) * 16, -(-x.shape[3] // 32) * 32
+    return (h, w) != tuple(x.shape[2:]) and conv3x3_s2_supported(x[:, :, :1, :1].expand(-1, -1, h, w), weight)
 
 
 S2_BWD_OWN = True
@@ -1417,10 +1456,12 @@ class ConvS2Fn(torch.autograd.Function):
         co = w.shape[0]
         if S2_BWD_OWN and h % 2 == 0 and wd % 2 == 0 and conv3x3_wanted((b, co, h, wd), (c, co, 3, 3)):
             dy = _dev(dy, "dy")
+            routes.note("conv3x3_s2.bwd_data", "zero_stuffed")
             up = torch.zeros(b, co, h, wd, device=dy.device, dtype=torch.float32)
             o = 0 if ctx.pad == 1 else 1
             up[:, :, o::2, o::2] = dy
             return _conv3x3_run(up, w, True, None, None, c), None, None, None
+        routes.note("conv3x3_s2.bwd_data", "lib")
         if ctx.pad == 1:
             return torch.nn.grad.conv2d_input(ctx.xshape, w, dy.contiguous(), stride=2, padding=1), None, None, None
         dxp = torch.nn.grad.conv2d_input((b, c, h + 1, wd + 1), w, dy.contiguous(), stride=2, padding=0)   # pad 0 = (0,1,0,1) extension
@@ -1439,6 +1480,7 @@ def conv3x3_s2(x, weight, bias=None, pad: int = 0, want_stats: bool = False):
 
 def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
     x = _dev(x.detach(), "x")
+    routes.note("conv3x3_s2", "s2_direct")
     U = _filters(weight, "s2")
     B, ci, H, W = x.shape
     co = weight.shape[0]

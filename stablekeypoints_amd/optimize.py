@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import dist as skp_dist
 from . import ops, ptp_utils
+from . import routes as _routes
 from ._maps import collect_maps, collect_maps_batched          # noqa: F401  (collect_maps is public API)
 from .eval import find_k_max_pixels
 from .invertable_transform import RandomAffineWithInverse
@@ -334,8 +335,14 @@ class GraphedStep:
         graph = torch.cuda.CUDAGraph()
         # kept values of the frozen weights (filters, stacks, offsets, the time embedding) that the graph reads: held with it, so an
         # eager step of another group size that replaces them in its caches cannot free them under the replays
-        with ops.recording() as held, torch.cuda.graph(graph):
-            self._body(st)
+        # the recording runs every gate but launches nothing: its notes leave the route ledger again and come back once per replay
+        before = _routes.snapshot()
+        try:
+            with ops.recording() as held, torch.cuda.graph(graph):
+                self._body(st)
+        finally:
+            st["routes"] = _routes.delta(before)
+            _routes.merge(st["routes"], -1)
         st["graph"], st["held"] = graph, held
 
     def _stage(self, st, images, thetas, noise):
@@ -383,13 +390,14 @@ class GraphedStep:
         self.transform.last_theta_host = thetas
         self._stage(st, images, thetas, noise)
         st["graph"].replay()
+        _routes.merge(st["routes"])                               # what the recorded gates chose ran once more
         out = st["out"]
         return out[0], out[1], out[2]
 
 
 def optimize_embedding(ldm, args, controllers, num_gpus, context=None,
                        from_where=["down_cross", "mid_cross", "up_cross"], draws=None, trajectory_out=None,
-                       step_callback=None):
+                       step_callback=None, routes="off"):
     """Reference signature (optimize.py:269-276).  `num_gpus` = devices driven by THIS process (1); the
     data-parallel width is `num_gpus * world_size`.  Returns the detached embedding [1,T,768].
     `draws = (order, noise, thetas)` injects THIS rank's image order [steps*accum], the noise of every forward in the
@@ -398,7 +406,15 @@ def optimize_embedding(ldm, args, controllers, num_gpus, context=None,
     `trajectory_out`, a list, receives the embedding after every optimizer step; `step_callback(step)` runs after every
     optimizer step (tools/protocol_bench.py reads its clocks there).  Images come through `GroupLoader`: the reference's
     `DataLoader` iteration (optimize.py:333-347) as a one-group-ahead host pipeline (`args.loader_workers`, 0 = the
-    synchronous loop); the image ORDER is the same either way."""
+    synchronous loop); the image ORDER is the same either way.
+    `routes`: "off"; "report" resets the route ledger first, so that `routes.table()` afterwards describes this run; "strict" also
+    runs the loop under `routes.strict(allow=routes.DOCUMENTED_LIBRARY_ROUTES)`: a gate that leaves the HIP kernels for an
+    undocumented library / eager route raises where it does so (the rule ends with the call, however it ends)."""
+    with _routes.guard(routes):
+        return _optimize_embedding(ldm, args, controllers, num_gpus, context, from_where, draws, trajectory_out, step_callback)
+
+
+def _optimize_embedding(ldm, args, controllers, num_gpus, context, from_where, draws, trajectory_out, step_callback):
     world, rank = skp_dist.world_size(), skp_dist.rank()
     width = num_gpus * world
     if args.batch_size < width or args.batch_size % width:

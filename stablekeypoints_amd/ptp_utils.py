@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import routes
 from .ldm.unet import StopForward
 from ._maps import FusedAttn, collect_maps
 
@@ -166,6 +167,7 @@ def _attention_core(module, q, k, v, is_cross=False):
             return ops.self_attention(q, k, v, module.heads, module.scale)
         raise RuntimeError(f"attention with {module.heads} heads of {q.shape[-1] // module.heads} channels has no HIP kernel "
                            f"(built head sizes: {ops.CROSS_ATTN_HEAD_DIMS}); there is no eager fallback on the GPU")
+    routes.note("attn.cross" if is_cross else "attn.self", "host")
     qh = module.reshape_heads_to_batch_dim(q)
     kh = module.reshape_heads_to_batch_dim(k)
     vh = module.reshape_heads_to_batch_dim(v)
@@ -354,8 +356,10 @@ def _ranked(score, argmax, R, top_k):
     n = score.shape[0]
     top_k = min(int(top_k), n)
     if 2 <= top_k <= ops.SELECT_MAX_CANDIDATES and n <= ops.SELECT_MAX_TOKENS:
+        routes.note("select.rank", "select_kernel")
         cand, _ = ops.select_tokens(score, argmax, R, top_k, 2)
         return cand
+    routes.note("select.rank", "sort")
     return torch.sort(score, stable=True).indices[:top_k]
 
 
