@@ -48,7 +48,8 @@ int skp_abi_version(void);
  * environment variables).  Keys: "wino_split" (force the K split of the F(4x4,3x3) launches), "wino_raw_max_tiles" (widen the
  * raw-filter form's gate), "map_bands" (band count of the token-major map backward), "fa2_two_kernel_bwd" (1: the two-kernel
  * flash backward at the fused form's shapes), "gn_fold_max_cout", "cross_attn_ts" (1: the 128-query
- * cross-attention kernels where the token-split form would run).  value 0 = the library's own choice.  Process-global, not
+ * cross-attention kernels where the token-split form would run), "conv_s2w" (1: the polyphase Winograd stride-2 kernel wherever it
+ * can run, 2: nowhere).  value 0 = the library's own choice.  Process-global, not
  * thread-safe.  Returns 0 / the value, SKP_E_RANGE for an unknown key. */
 int skp_tune_set(const char* key, int value);
 int skp_tune_get(const char* key);
@@ -360,6 +361,23 @@ int skp_conv3x3_s2_f32(const void* x, const void* U, const void* bias, void* y, 
 int64_t skp_conv3x3_s2_workspace(int B, int Cin, int Cout, int H, int W);
 int skp_conv3x3_s2_ws_f32(const void* x, const void* U, const void* bias, void* y, void* workspace, int B, int Cin, int Cout,
                           int H, int W, int pad, void* stream);
+
+/* The pad = 0 stride-2 convolution as a polyphase Winograd F(4x4,2x2) (skp_conv_s2w.hip): the four pixel phases of the input
+ * see 2x2, 2x1, 1x2 and 1x1 filters, i.e. one stride-1 2x2 convolution over 4 Cin channels; 81 multiplies per 16 outputs and
+ * channel pair instead of 144.  Same result as skp_conv3x3_s2_f32 up to fp32 rounding (relative error ~1e-6 of the output
+ * maximum); no K split, no workspace, bit-identical from call to call.
+ *   skp_conv3x3_s2w_ok         1 where this kernel is the faster one (measured shape rule; "conv_s2w" tune key: 1 all, 2 none)
+ *   skp_conv3x3_s2w_filter_f32 one-off transform of a frozen weight w [Cout,Cin,3,3] (fp64, rounded once) into
+ *                              U [Cin/16][81][4][Cout][4]: the non-zero (position, phase) blocks in the order the kernel reads them
+ *   skp_conv3x3_s2w_stats_f32  + stats [B][Cout][(H/8)*(W/8)/16][2] = {mean, sum (y - mean)^2} per block of 16 consecutive 4x4
+ *                              output tiles (256 pixels; (H/8)*(W/8) % 16 == 0), for skp_group_norm_fwd_blocks_f32
+ * Limits: pad = 0, Cin % 16 == 0, Cout % 128 == 0, H % 8 == 0, W % 8 == 0, x, U, y < 2 GiB each, else SKP_E_RANGE; bias may be NULL. */
+int skp_conv3x3_s2w_ok(int B, int Cin, int Cout, int H, int W, int pad);
+int skp_conv3x3_s2w_filter_f32(const void* w, void* U, int Cout, int Cin, int pad, void* stream);
+int skp_conv3x3_s2w_f32(const void* x, const void* U, const void* bias, void* y, int B, int Cin, int Cout, int H, int W,
+                        int pad, void* stream);
+int skp_conv3x3_s2w_stats_f32(const void* x, const void* U, const void* bias, void* y, float* stats, int B, int Cin, int Cout,
+                              int H, int W, int pad, void* stream);
 
 /* 3x3 / stride 1 / padding 1 convolution with AT MOST FOUR input channels (the `conv_in` layers: VAE encoder 3 -> 128 on the
  * image, ptp_utils.py:289-304; UNet 4 -> 320 on the latents, ptp_utils.py:227), forward, NCHW, bias folded in (may be NULL).

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Build-time guard for the NAMED accumulators of skp_conv_wino4.hip (skp_wino4_common.h: positions 0-31 of the 36 Winograd
-accumulators live in a[0:255] through inline-assembly MFMAs; the compiler is told the AGPR file is clobbered by every such
+"""Build-time guard for the NAMED accumulators of skp_conv_wino4.hip and skp_conv_s2w.hip (skp_wino4_common.h: positions 0-31 of the
+36 Winograd accumulators -- all 25 positions of the stride-2 F(4x4,2x2) kernel -- live in a[0:255] through inline-assembly MFMAs; the compiler is told the AGPR file is clobbered by every such
 statement, but nothing in the language stops a future compiler from parking a value of its own there BETWEEN two statements).
 
-usage: check_agpr.py <object.o>      (run by the Makefile after skp_conv_wino4.o is built; non-zero exit fails the build)
+usage: check_agpr.py <object.o>      (run by the Makefile after skp_conv_wino4.o / skp_conv_s2w.o is built; non-zero exit fails the build)
 
 For every kernel of the object that uses AGPRs it checks, on the disassembly of the gfx950 code object:
   * the only instructions that touch an AGPR are v_mfma_* (accumulate in place), v_accvgpr_read_b32 (epilogue) and

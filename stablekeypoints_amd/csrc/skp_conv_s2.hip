@@ -2,8 +2,10 @@
 // bias folded in: the down-sampling convolutions of the frozen VAE encoder (diffusers Downsample2D with padding 0:
 // F.pad(x, (0,1,0,1)) then conv(stride 2) [third party], reached from ptp_utils.py:289-304 `image2latent`) and the UNet's
 // Downsample2D (padding 1).  On the library path these three VAE layers cost the step 3.7 ms of implicit-GEMM kernels at
-// ~0.5 of the fp32 peak plus 1.5 ms of NCHW<->NHWC transposes plus 1 ms of F.pad copies; Winograd does not apply to
-// stride 2, but a direct form needs no transform arithmetic at all, so nearly every issued instruction is an MFMA.
+// ~0.5 of the fp32 peak plus 1.5 ms of NCHW<->NHWC transposes plus 1 ms of F.pad copies.  A direct form needs no transform
+// arithmetic at all, so nearly every issued instruction is an MFMA.  Winograd does apply to stride 2 after a split of the input
+// into its pixel phases: skp_conv_s2w.hip (F(4x4,2x2), 81 multiplies where this kernel does 144) takes the pad-0 launches that
+// fill the chip (skp_conv3x3_s2w_ok); this kernel keeps pad 1, the K-split small grids and every other shape.
 //
 //   y[b,co,oy,ox] = bias[co] + sum_{ci,a,c} w[co,ci,a,c] * x[b,ci, 2 oy + a - p, 2 ox + c - p]      (out of range = 0)
 //   p = 0: the asymmetric (0,1,0,1) padding of the VAE;  p = 1: symmetric padding 1.   OH = H/2, OW = W/2.

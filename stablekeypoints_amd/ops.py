@@ -986,7 +986,8 @@ def conv3x3_supported(x_shape, w_shape, need_grad=True):
 _FILTER_FORMS = {"f2": ("skp_conv3x3_filter_f32", 16),          # Winograd F(2x2,3x3)
                  "f4": ("skp_conv3x3_f4_filter_f32", 36),       # Winograd F(4x4,3x3)
                  "f4r": ("skp_conv3x3_f4r_filter_f32", 9),      # raw-filter form: the 9 taps in MFMA operand order
-                 "s2": ("skp_conv3x3_s2_filter_f32", 9)}        # stride-2 direct kernel
+                 "s2": ("skp_conv3x3_s2_filter_f32", 9),        # stride-2 direct kernel
+                 "s2w": ("skp_conv3x3_s2w_filter_f32", 81)}     # stride-2 polyphase Winograd F(4x4,2x2), pad 0
 
 
 def _filters(weight, form, backward=False):
@@ -999,6 +1000,8 @@ def _filters(weight, form, backward=False):
         U = torch.empty(per_pair * co * ci, device=w.device, dtype=torch.float32)
         if form == "s2":
             N.check(N.lib().skp_conv3x3_s2_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, _stream()), name)
+        elif form == "s2w":
+            N.check(N.lib().skp_conv3x3_s2w_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, 0, _stream()), name)
         else:
             N.check(getattr(N.lib(), name)(w.data_ptr(), U.data_ptr(), *((ci, co, 1) if backward else (co, ci, 0)), _stream()), name)
         return U
@@ -1480,11 +1483,24 @@ def conv3x3_s2(x, weight, bias=None, pad: int = 0, want_stats: bool = False):
 
 def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
     x = _dev(x.detach(), "x")
-    routes.note("conv3x3_s2", "s2_direct")
-    U = _filters(weight, "s2")
     B, ci, H, W = x.shape
     co = weight.shape[0]
     y = torch.empty(B, co, H // 2, W // 2, device=x.device, dtype=torch.float32)
+    if N.lib().skp_conv3x3_s2w_ok(B, ci, co, H, W, int(pad)):       # polyphase Winograd F(4x4,2x2) where it was measured faster
+        routes.note("conv3x3_s2", "s2_wino")
+        U = _filters(weight, "s2w")
+        nblk = (H // 8) * (W // 8) // 16
+        if want_stats and GN_FUSED_STATS and nblk * 16 == (H // 8) * (W // 8):
+            stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
+            N.check(N.lib().skp_conv3x3_s2w_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), stats.data_ptr(),
+                                                      B, ci, co, H, W, int(pad), _stream()), "skp_conv3x3_s2w_stats_f32")
+            y._skp_blocks = (stats, nblk, 256)
+            return y
+        N.check(N.lib().skp_conv3x3_s2w_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), B, ci, co, H, W, int(pad),
+                                            _stream()), "skp_conv3x3_s2w_f32")
+        return y
+    routes.note("conv3x3_s2", "s2_direct")
+    U = _filters(weight, "s2")
     if want_stats and GN_FUSED_STATS:
         nblk = (H // 16) * (W // 32)
         stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)

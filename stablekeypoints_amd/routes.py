@@ -42,7 +42,7 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "conv3x3.bwd_data": dict(_WINO),
     "conv_in": {"small": "hip"},                          # <= 4 input channels, forward only (ops.conv3x3_small)
     "conv_out": {"lib": "library"},                       # <= 8 output channels: below the Winograd kernels' channel blocks
-    "conv3x3_s2": {"s2_direct": "hip"},                   # ops._conv3x3_s2_raw
+    "conv3x3_s2": {"s2_direct": "hip", "s2_wino": "hip"},  # ops._conv3x3_s2_raw: direct / polyphase Winograd F(4x4,2x2)
     "conv3x3_s2.bwd_data": {"zero_stuffed": "hip", "lib": "library"},
     "downsample": {"s2_direct": "hip", "eager": "eager"},
     "downsample.untiled": {"eager": "eager"},             # input no multiple of the stride-2 kernel's 16 x 32 pixel tile

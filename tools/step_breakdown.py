@@ -14,7 +14,7 @@ import sys
 F32_MATRIX_PEAK_TF = 157.3
 
 CLASSES = [
-    ("skp conv3x3 (Winograd stride 1 + direct stride 2)", ("skp_wino", "skp_conv_s2")),
+    ("skp conv3x3 (Winograd stride 1 + direct stride 2)", ("skp_wino", "skp_conv_s2", "skp_s2w")),
     ("skp flash attention (self + long-key cross)", ("skp_self_attn", "skp_fa2_", "skp_fas_")),
     ("skp attention map fwd/bwd (north-star kernel)", ("skp_attn_map", "skp_map_")),
     ("skp fused GroupNorm+SiLU / bias+residual / add+LayerNorm", ("skp_group_norm", "skp_gn_", "skp_add_bias", "skp_add_ln")),
@@ -53,7 +53,7 @@ def main():
     for st, en, name, grid in rows:
         if st < t0 or en > t1:
             continue
-        if any(k in name for k in ("skp_wino", "skp_conv_s2", "skp_fa2_", "skp_self_attn", "skp_attn_map", "skp_map_", "Cijk")):
+        if any(k in name for k in ("skp_wino", "skp_conv_s2", "skp_s2w", "skp_fa2_", "skp_self_attn", "skp_attn_map", "skp_map_", "Cijk")):
             short = name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")[:70]
             sh = shapes.setdefault((short, grid), [0.0, 0])
             sh[0] += en - st; sh[1] += 1
