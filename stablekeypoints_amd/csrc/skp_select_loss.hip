@@ -133,7 +133,11 @@ extern "C" int skp_token_stats_f32(const float* M, int T, int R, int num_subject
 
 __device__ __forceinline__ float skp_dist(float ay, float ax, float by, float bx) {
     const float dy = __fsub_rn(ay, by), dx = __fsub_rn(ax, bx);     // no fma contraction: keep ties exact
-    return __fsqrt_rn(__fadd_rn(__fmul_rn(dy, dy), __fmul_rn(dx, dx)));
+    // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS that intrinsic is the native v_sqrt_f32 (about 1 ulp, not
+    // correctly rounded), while sqrtf is correctly rounded in HIP device code (-fhip-fp32-correctly-rounded-divide-sqrt, the
+    // default).  Locations that differ only by the rounding of (row + 0.5) / R give distances one ulp apart: the order of
+    // the picks is the reference's only with an IEEE square root.
+    return sqrtf(__fadd_rn(__fmul_rn(dy, dy), __fmul_rn(dx, dx)));
 }
 
 // blockIdx.x = image of a batch (skp_select_tokens_batched): every pointer advances by its per-image stride
