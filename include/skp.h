@@ -49,7 +49,7 @@ int skp_abi_version(void);
  * raw-filter form's gate), "map_bands" (band count of the token-major map backward), "fa2_two_kernel_bwd" (1: the two-kernel
  * flash backward at the fused form's shapes), "gn_fold_max_cout", "cross_attn_ts" (1: the 128-query
  * cross-attention kernels where the token-split form would run), "conv_s2w" (1: the polyphase Winograd stride-2 kernel wherever it
- * can run, 2: nowhere).  value 0 = the library's own choice.  Process-global, not
+ * can run, 2: nowhere), "conv_up2" (the same for the up-sampling convolution skp_conv3x3_up2_f32).  value 0 = the library's own choice.  Process-global, not
  * thread-safe.  Returns 0 / the value, SKP_E_RANGE for an unknown key. */
 int skp_tune_set(const char* key, int value);
 int skp_tune_get(const char* key);
@@ -391,6 +391,33 @@ int skp_conv3x3_small_f32(const void* x, const void* w, const void* bias, void* 
 int skp_conv3x3_small_stats_blocks(int B, int Cin, int Cout, int H, int W);
 int skp_conv3x3_small_stats_f32(const void* x, const void* w, const void* bias, void* y, float* stats, int B, int Cin, int Cout,
                                 int H, int W, void* stream);
+
+/* Nearest-neighbour 2x up-sampling + 3x3 / stride 1 / padding 1 convolution (Upsample2D: the VAE decoder's and the UNet's
+ * up-samplers in the sampling loop of ptp_utils.py `text2image_ldm_stable`) without writing the up-sampled tensor
+ * (skp_conv_up2.hip): output pixel (2i+a, 2j+c) is a 2x2 convolution of the LOW-resolution input with one of four phase filters
+ * (row phase 0: rows {i-1: w0, i: w1+w2}; phase 1: {i: w0+w1, i+1: w2}; columns alike), a direct implicit GEMM on the fp32 matrix
+ * cores, 4 multiplies per output.  Forward only, frozen weights; no K split, no workspace, bit-identical from call to call.
+ *   x [B,Cin,H,W] -> y [B,Cout,2H,2W];  H, W: the low-resolution size.
+ *   skp_conv3x3_up2_ok         1 where this kernel is the route of choice (measured shape rule; "conv_up2" tune key: 1 every
+ *                              shape it can run, 2 none)
+ *   skp_conv3x3_up2_filter_f32 one-off fold of a frozen weight w [Cout,Cin,3,3] (fp64, rounded once) into
+ *                              U [4 phases 2a+c][4 taps 2dr+dc][Cin/16][4][Cout][4], 16 * Cin * Cout floats
+ * Limits: Cin % 16 == 0, Cout % 32 == 0, x, U, y < 2 GiB each, else SKP_E_RANGE; bias may be NULL. */
+int skp_conv3x3_up2_ok(int B, int Cin, int Cout, int H, int W);
+int skp_conv3x3_up2_filter_f32(const void* w, void* U, int Cout, int Cin, void* stream);
+int skp_conv3x3_up2_f32(const void* x, const void* U, const void* bias, void* y, int B, int Cin, int Cout, int H, int W,
+                        void* stream);
+
+/* 3x3 / stride 1 / padding 1 convolution to AT MOST FOUR output channels (the VAE decoder's `conv_out`, 128 -> 3 on the image,
+ * ptp_utils.py `latent2image`), forward, NCHW, bias folded in (may be NULL); VALU kernel, two pixels per thread, wave-uniform
+ * weights.  w: the module's own [Cout,Cin,3,3].  image != 0: the epilogue writes clamp(y / 2 + 0.5, 0, 1) instead of y.
+ * Limits: Cin % 16 == 0, Cout <= 4, W even, B <= 65535, else SKP_E_RANGE. */
+int skp_conv3x3_small_out_f32(const void* x, const void* w, const void* bias, void* y, int B, int Cin, int Cout, int H, int W,
+                              int image, void* stream);
+
+/* y[i] = a * x[i] + b * z[i] for i < n (y may alias x or z): the eta = 0 DDIM update x_prev = c1 x_t + c2 eps with the two
+ * coefficients computed on the host (ldm/scheduler.py DDIMScheduler.step). */
+int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, float b, void* stream);
 
 /* GEGLU of the transformer feed-forward (diffusers attention.GEGLU [third party], inside the hooked UNet forward):
  *   y[r, c] = p[r, c] * gelu(p[r, inner + c])    p: [rows, 2*inner], y: [rows, inner], exact (erf) gelu, inner % 4 == 0

@@ -15,7 +15,8 @@ import torch.nn.functional as F
 from .. import ops
 from .. import routes
 from .attention import AttentionBlock, BasicTransformerBlock, Transformer2DModel
-from .unet import Downsample2D, ResnetBlock2D, UNet2DConditionModel
+from .unet import Downsample2D, ResnetBlock2D, UNet2DConditionModel, Upsample2D
+from .vae import Decoder
 
 
 def _resnet_forward(m: ResnetBlock2D):
@@ -188,6 +189,45 @@ def _downsample_forward(m):
     return forward
 
 
+def _upsample_forward(m: Upsample2D, always: bool):
+    """Upsample2D: nearest 2x + 3x3 convolution as one kernel on the low-resolution input (ops.conv3x3_up2, which notes its route
+    at the `upsample_conv` site).  `always`: the VAE decoder's up-samplers, which only ever run while sampling; the UNet's take it
+    inside `ops.up2_in_unet()` alone -- everywhere else they run their own forward (interpolate + the patched convolution), route
+    for route what the optimisation path has always noted."""
+    def forward(x):
+        frozen = not (m.conv.weight.requires_grad or (m.conv.bias is not None and m.conv.bias.requires_grad))
+        if ((always or ops.up2_in_unet_enabled()) and frozen and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and not (torch.is_grad_enabled() and x.requires_grad)):
+            return ops.conv3x3_up2(x, m.conv.weight, m.conv.bias)
+        return m.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))    # the module's own forward: its convolution notes the route
+    return forward
+
+
+def _decoder_forward(m: Decoder):
+    """VAE decoder: its resnets, mid-block attention, conv_in (4 -> C: the small-input kernel through the patched Conv2d) and
+    up-samplers are patched module by module; this forward adds the tail -- GroupNorm + SiLU on the fused kernel and `conv_out`
+    (C -> 3) on the small-output kernel, whose epilogue also makes the [0, 1] image when asked."""
+    orig = m.forward
+
+    def forward(z, to_image=False):
+        if not (z.is_cuda and z.dtype == torch.float32 and not torch.is_grad_enabled()):
+            routes.note("vae.decoder", "eager")
+            return orig(z, to_image=to_image)
+        routes.note("vae.decoder", "fused")
+        with ops.conv3x3_own_kernels():              # (few-tile launches of a reduced-width tree stay on the HIP kernels)
+            h = m.mid_block(m.conv_in(z))
+            for blk in m.up_blocks:
+                h = blk(h)
+        h = (ops.group_norm_silu(h, m.conv_norm_out) if ops.group_norm_supported(h, m.conv_norm_out.num_groups)
+             else F.silu(m.conv_norm_out(h)))
+        co = m.conv_out
+        if ops.conv3x3_small_out_ok(h, co.weight) and co.padding == (1, 1) and co.stride == (1, 1):
+            return ops.conv3x3_small_out(h, co.weight, co.bias, image=to_image)
+        y = co(h)                                    # (the patched Conv2d notes conv_out / lib)
+        return (y / 2 + 0.5).clamp(0, 1) if to_image else y
+    return forward
+
+
 def _vae_encode(m):
     """`AutoencoderKL.encode` with the encoder's tail as ONE Winograd launch: `quant_conv` (1 x 1, 8 -> 8) after `conv_out` (3 x 3,
     512 -> 8) is a single 3 x 3 convolution with the composed filter `Wq . Wout` and bias `Wq . b_out + b_q` (exact algebra; the
@@ -237,7 +277,14 @@ def _vae_encode(m):
 
 def fuse_norms(module: torch.nn.Module) -> int:
     n = 0
+    decoder_ups = {id(u) for d in module.modules() if isinstance(d, Decoder) for u in d.modules() if isinstance(u, Upsample2D)}
     for mod in module.modules():
+        if isinstance(mod, Decoder) and "forward" not in mod.__dict__:
+            mod.forward = _decoder_forward(mod); n += 1
+            continue
+        if isinstance(mod, Upsample2D) and "forward" not in mod.__dict__:
+            mod.forward = _upsample_forward(mod, id(mod) in decoder_ups)    # (its .conv is patched below like any 3 x 3 Conv2d)
+            continue
         if mod.__class__.__name__ == "AutoencoderKL" and hasattr(mod, "quant_conv") and "encode" not in mod.__dict__:
             mod.encode = _vae_encode(mod); n += 1
             continue

@@ -9,7 +9,8 @@ Weights.  There is no network, so checkpoints come from a LOCAL DIRECTORY only:
   * `<dir>/unet.pt`, `<dir>/vae.pt` (state dicts with the diffusers keys), or the diffusers layout
     `<dir>/unet/diffusion_pytorch_model.{safetensors,bin}` (+ `config.json`), `<dir>/vae/...`;
   * loaded with `weights_only=True` and checked key by key: a missing or shape-mismatched key RAISES (the only
-    tolerated leftovers are the VAE decoder half, which is not on this path).
+    tolerated leftovers are the VAE decoder half when the decoder was not asked for; with `with_decoder=True` the decoder keys
+    are loaded and checked like every other).
 SEEDED SYNTHETIC weights (PyTorch default inits under a fixed CPU generator seed => identical on every box) are built
 only when the caller names them explicitly: `synthetic-<arch>`, `<arch>` from `ARCHS`, or any `tiny*` name.  A hub id
 such as `sd-legacy/stable-diffusion-v1-5` that is not a local directory raises `FileNotFoundError` -- optimising
@@ -132,11 +133,13 @@ class StableDiffusionPipeline:
         self.arch, self.synthetic_weights = arch, synthetic
 
     @staticmethod
-    def build(arch: str, seed=0, unet_kwargs=None, init_device=None):
+    def build(arch: str, seed=0, unet_kwargs=None, init_device=None, with_decoder=False):
         """Module trees with seeded default inits.  `init_device=None`: parameters are drawn on the CPU (identical on
         every box, and on CPU and GPU runs -- what the parity tests rely on).  `init_device="cuda:N"`: drawn directly
         on that GPU from its own seeded generator (identical on every rank of a job, different numbers from the CPU
-        draw): N ranks of a multi-GPU run do not contend for the host cores with N x 3.4 GB of CPU-side init."""
+        draw): N ranks of a multi-GPU run do not contend for the host cores with N x 3.4 GB of CPU-side init.
+        `with_decoder`: the VAE's decoder half is added AFTER everything else, from a generator of its own (seed + 1, always drawn
+        on the CPU): the UNet's and the encoder's numbers are the same with and without it."""
         cfg = ARCHS[arch]
         on_gpu = init_device is not None and torch.device(init_device).type == "cuda"
         gen_state = torch.random.get_rng_state()
@@ -154,19 +157,21 @@ class StableDiffusionPipeline:
             torch.random.set_rng_state(gen_state)
             if on_gpu:
                 torch.cuda.set_rng_state(cuda_state, init_device)
+        if with_decoder:
+            vae.add_decoder(seed + 1)
         return unet, vae
 
     @classmethod
     def from_pretrained(cls, type="sd-legacy/stable-diffusion-v1-5", use_auth_token=None, scheduler=None, seed=0,
-                        init_device=None):
+                        init_device=None, with_decoder=False):
         name = str(type)
         sched = scheduler if scheduler is not None else DDIMScheduler()
         if os.path.isdir(name):
             cfg_path = os.path.join(name, "unet", "config.json")
             arch = guess_arch(os.path.basename(os.path.normpath(name)))
             kw = _unet_kwargs_from_config(cfg_path) if os.path.exists(cfg_path) else None
-            unet, vae = cls.build(arch, seed, kw)
-            for sub, mod, allowed in (("unet", unet, ()), ("vae", vae, ("decoder.", "post_quant_conv."))):
+            unet, vae = cls.build(arch, seed, kw, with_decoder=with_decoder)
+            for sub, mod, allowed in (("unet", unet, ()), ("vae", vae, () if with_decoder else ("decoder.", "post_quant_conv."))):
                 state = _read_state(os.path.join(name, sub))
                 if state is None:
                     raise FileNotFoundError(f"{name}: no {sub}.pt and no {sub}/diffusion_pytorch_model.(safetensors|bin)")
@@ -183,7 +188,7 @@ class StableDiffusionPipeline:
             arch = guess_arch(name)
             warnings.warn(f"'{name}' not found locally: building the {arch} architecture with SEEDED SYNTHETIC weights "
                           "(SKP_ALLOW_SYNTHETIC=1) -- keypoints optimised against it are meaningless", stacklevel=2)
-        unet, vae = cls.build(arch, seed, init_device=init_device)
+        unet, vae = cls.build(arch, seed, init_device=init_device, with_decoder=with_decoder)
         unet.eval(); vae.eval()
         return cls(unet, vae, sched, arch, synthetic=True)
 

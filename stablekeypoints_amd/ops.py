@@ -987,7 +987,8 @@ _FILTER_FORMS = {"f2": ("skp_conv3x3_filter_f32", 16),          # Winograd F(2x2
                  "f4": ("skp_conv3x3_f4_filter_f32", 36),       # Winograd F(4x4,3x3)
                  "f4r": ("skp_conv3x3_f4r_filter_f32", 9),      # raw-filter form: the 9 taps in MFMA operand order
                  "s2": ("skp_conv3x3_s2_filter_f32", 9),        # stride-2 direct kernel
-                 "s2w": ("skp_conv3x3_s2w_filter_f32", 81)}     # stride-2 polyphase Winograd F(4x4,2x2), pad 0
+                 "s2w": ("skp_conv3x3_s2w_filter_f32", 81),     # stride-2 polyphase Winograd F(4x4,2x2), pad 0
+                 "up2": ("skp_conv3x3_up2_filter_f32", 16)}     # up-sampling convolution: four 2x2 phase filters
 
 
 def _filters(weight, form, backward=False):
@@ -998,8 +999,8 @@ def _filters(weight, form, backward=False):
         co, ci = w.shape[:2]
         name, per_pair = _FILTER_FORMS[form]
         U = torch.empty(per_pair * co * ci, device=w.device, dtype=torch.float32)
-        if form == "s2":
-            N.check(N.lib().skp_conv3x3_s2_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, _stream()), name)
+        if form in ("s2", "up2"):
+            N.check(getattr(N.lib(), name)(w.data_ptr(), U.data_ptr(), co, ci, _stream()), name)
         elif form == "s2w":
             N.check(N.lib().skp_conv3x3_s2w_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, 0, _stream()), name)
         else:
@@ -1075,11 +1076,29 @@ def conv3x3_f4_ok(x_shape, w_shape):
     return b * (h // 4) * (w // 4) >= 32 or conv3x3_f4r_ok(x_shape, int(w_shape[0]))
 
 
+_CONV3X3_OWN_ONLY = False
+
+
+@contextlib.contextmanager
+def conv3x3_own_kernels():
+    """Inside the block `conv3x3_wanted` drops its tile-count rule: every shape the Winograd kernels can run takes them.  The VAE
+    decoder runs in it (ldm/fused.py): a one-image latency path, whose full-width launches pass the tile rule anyway (one 64^2
+    latent is 256 tiles) -- only reduced-width trees at 8^2 differ, and those then stay on the HIP kernels instead of the library."""
+    global _CONV3X3_OWN_ONLY
+    prev, _CONV3X3_OWN_ONLY = _CONV3X3_OWN_ONLY, True
+    try:
+        yield
+    finally:
+        _CONV3X3_OWN_ONLY = prev
+
+
 def conv3x3_wanted(x_shape, w_shape):
     """Supported AND enough tiles to fill the MFMA column blocks (layers with few workgroups are split over input
     channels inside the library call, so the channel counts do not matter here)."""
     if CONV3X3_MODE == "lib" or not conv3x3_supported(x_shape, w_shape):
         return False
+    if _CONV3X3_OWN_ONLY:
+        return True
     b, _, h, w = (int(v) for v in x_shape)
     return conv3x3_f4_ok(x_shape, w_shape) or b * ((h + 1) // 2) * ((w + 1) // 2) >= 128
 
@@ -1279,6 +1298,93 @@ def conv3x3_small(x, weight, bias=None, want_stats=False):
         return y
     N.check(N.lib().skp_conv3x3_small_f32(x.data_ptr(), w.data_ptr(), bb.data_ptr() if bb is not None else None, y.data_ptr(),
                                           B, ci, w.shape[0], H, W, _stream()), "skp_conv3x3_small_f32")
+    return y
+
+
+def conv3x3_small_out(x, weight, bias=None, image=False):
+    """3x3 / stride 1 / padding 1 convolution to <= 4 output channels (the VAE decoder's conv_out), forward only; `image`: the
+    epilogue writes clamp(y / 2 + 0.5, 0, 1), the [-1, 1] -> [0, 1] map of `ptp_utils.latent2image`, instead of y."""
+    x, w = _dev(x.detach(), "x"), _dev(weight.detach(), "weight")
+    routes.note("conv_out", "small_out")
+    B, ci, H, W = x.shape
+    y = torch.empty(B, w.shape[0], H, W, device=x.device, dtype=torch.float32)
+    bb = _dev(bias.detach(), "bias") if bias is not None else None
+    N.check(N.lib().skp_conv3x3_small_out_f32(x.data_ptr(), w.data_ptr(), _ptr(bb), y.data_ptr(), B, ci, w.shape[0], H, W,
+                                              int(bool(image)), _stream()), "skp_conv3x3_small_out_f32")
+    return y
+
+
+def conv3x3_small_out_ok(x, weight) -> bool:
+    """Shapes `conv3x3_small_out` takes: Cin % 16 == 0, Cout <= 4, even width, 3x3 taps."""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and CONV3X3_MODE != "lib"
+            and int(weight.shape[1]) == x.shape[1] and x.shape[1] % 16 == 0 and weight.shape[0] <= 4 and x.shape[3] % 2 == 0
+            and x.shape[0] <= 65535)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# nearest 2x up-sampling + 3x3 convolution (Upsample2D) without the up-sampled tensor; forward only (sampling runs under no_grad)
+# ---------------------------------------------------------------------------------------------------------
+def up2_fold_filter(weight):
+    """The four 2x2 phase filters of `conv2d(interpolate(x, 2x, nearest), weight, padding=1)`: F [2, 2, Co, Ci, 2, 2] with
+    y[:, :, 2i+a, 2j+c] = sum_{ci,dr,dc} F[a, c, :, ci, dr, dc] * x[:, ci, i+a-1+dr, j+c-1+dc]   (out of range = 0).
+    Row phase 0 sees rows {i-1: w0, i: w1+w2}, phase 1 {i: w0+w1, i+1: w2}; columns fold the same way.  Plain torch in the
+    weight's own dtype and device: the restatement of csrc/skp_conv_up2.hip's filter fold that the tests compare against."""
+    m = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=weight.dtype, device=weight.device)   # [phase][tap][r]
+    return torch.einsum("adr,oirs,ces->acoide", m, weight, m)
+
+
+_UP2_IN_UNET = False
+
+
+@contextlib.contextmanager
+def up2_in_unet(on: bool = True):
+    """Inside the block the UNet's Upsample2D layers may take `conv3x3_up2` (the sampling loop of
+    ptp_utils.text2image_ldm_stable); outside -- the default -- they run interpolate + their own convolution, as the optimisation
+    path always has."""
+    global _UP2_IN_UNET
+    prev, _UP2_IN_UNET = _UP2_IN_UNET, bool(on)
+    try:
+        yield
+    finally:
+        _UP2_IN_UNET = prev
+
+
+def up2_in_unet_enabled() -> bool:
+    return _UP2_IN_UNET
+
+
+def conv3x3_up2(x, weight, bias=None):
+    """y = conv2d(interpolate(x, scale 2, nearest), weight, bias, padding=1) for a frozen weight, forward only: the polyphase
+    kernel on the low-resolution input where the library's gate (`skp_conv3x3_up2_ok`) takes the shape, else interpolate + the
+    Winograd route of `conv3x3_auto`.  Either way the choice is noted at the `upsample_conv` site."""
+    if weight.requires_grad or (bias is not None and bias.requires_grad):
+        raise RuntimeError("conv3x3_up2: frozen weights only")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("conv3x3_up2: forward only (no input gradient); run it under torch.no_grad()")
+    x = _dev(x.detach(), "x")
+    B, ci, H, W = x.shape
+    co = int(weight.shape[0])
+    if tuple(weight.shape[1:]) != (ci, 3, 3):
+        raise RuntimeError(f"conv3x3_up2: weight {tuple(weight.shape)} does not fit x {tuple(x.shape)}")
+    if CONV3X3_MODE != "lib" and N.lib().skp_conv3x3_up2_ok(B, ci, co, H, W):
+        routes.note("upsample_conv", "up2_poly")
+        U = _filters(weight, "up2")
+        y = torch.empty(B, co, 2 * H, 2 * W, device=x.device, dtype=torch.float32)
+        bb = _dev(bias.detach(), "bias") if bias is not None else None
+        N.check(N.lib().skp_conv3x3_up2_f32(x.data_ptr(), U.data_ptr(), _ptr(bb), y.data_ptr(), B, ci, co, H, W, _stream()),
+                "skp_conv3x3_up2_f32")
+        return y
+    routes.note("upsample_conv", "interp_wino")
+    return conv3x3_auto(torch.nn.functional.interpolate(x, scale_factor=2.0, mode="nearest"), weight, bias)
+
+
+def axpby(x, z, a: float, b: float):
+    """a * x + b * z in one pass (the DDIM update with host-computed coefficients)."""
+    x, z = _dev(x, "x"), _dev(z, "z")
+    if x.shape != z.shape:
+        raise RuntimeError("axpby: shapes differ")
+    y = torch.empty_like(x)
+    N.check(N.lib().skp_axpby_f32(x.data_ptr(), z.data_ptr(), y.data_ptr(), x.numel(), float(a), float(b), _stream()), "skp_axpby_f32")
     return y
 
 

@@ -2,7 +2,8 @@
 
 Kept names/signatures: `AttentionControl`, `AttentionStore`,
 `register_attention_control`, `find_pred_noise`, `run_and_find_attn`, `image2latent`,
-`find_top_k_gaussian`, `furthest_point_sampling`, `init_random_noise`.
+`find_top_k_gaussian`, `furthest_point_sampling`, `init_random_noise`, and the image-sampling entries `diffusion_step`,
+`latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461).
 
 What changes under the hood
   * the hooked cross-attention does NOT up-sample the layer input, re-project it and materialise a
@@ -257,6 +258,7 @@ def register_attention_control(model, controller, feature_upsample_res=256):
         if "up" in name:
             cross_att_count += register_recr(child, 0, "up")
     controller.num_att_layers = cross_att_count
+    model.__dict__["_skp_hook_controller"] = controller        # (the sampling loop empties the hooked store after every forward)
     assert cross_att_count != 0, ("No cross attention layers found in the model. The module tree must use the "
                                   "diffusers==0.8.0 `CrossAttention` layout.")
 
@@ -345,6 +347,115 @@ def run_and_find_attn(ldm, image, context, noise_level=-1, device="cuda",
                                            upsample_res=upsample_res, layers=layers, indices=indices))
         controllers[controller].reset()
     return attention_maps
+
+
+# ---------------------------------------------------------------------------------------------
+# image sampling from a learned embedding                reference ptp_utils.py:307-349,420-461
+# ---------------------------------------------------------------------------------------------
+def _unet_forward_shared_context(model, latents, t, context):
+    """One full UNet forward with the learned embedding as the context of every row (k / v projected once per layer width for
+    the shared row, as in `find_pred_noise`)."""
+    b = latents.shape[0]
+    try:
+        _context_kv_begin(model.unet, context, early_exit=False)
+        return model.unet(latents, t, context.expand(b, -1, -1) if context.shape[0] == 1 else context)["sample"]
+    finally:
+        _context_kv_end()
+        hooked = model.unet.__dict__.get("_skp_hook_controller")
+        if hooked is not None and hasattr(hooked, "reset"):
+            hooked.reset()                           # maps the hooks recorded during this forward belong to no optimisation step
+
+
+def diffusion_step(model, latents, context, t):
+    """ptp_utils.py:307-313: the noise prediction of `model.unet` for `latents` at timestep `t`, every row conditioned on `context`
+    ([1, T, D])."""
+    t = torch.as_tensor(t)
+    return _unet_forward_shared_context(model, latents, t.reshape(-1)[:1].repeat(latents.shape[0]), context)
+
+
+def latent2image(vae, latents):
+    """ptp_utils.py:316-322: latents / 0.18215 -> decode -> (x / 2 + 0.5).clamp(0, 1) -> uint8 numpy [B, H, W, 3].  (On the GPU the
+    [0, 1] map is the epilogue of the decoder's last convolution.)"""
+    with torch.no_grad():
+        image = _latent2float(vae, latents)
+    image = image.cpu().permute(0, 2, 3, 1).numpy()
+    return (image * 255).astype(np.uint8)
+
+
+def _latent2float(vae, latents):
+    vae = vae.module if isinstance(vae, torch.nn.DataParallel) else vae
+    return vae.decode(1 / 0.18215 * latents, to_image=True)["sample"]
+
+
+def _in_channels(unet):
+    return int(getattr(unet, "in_channels", None) or unet.config["in_channels"])
+
+
+def init_latent(latent, model, height, width, generator):
+    """ptp_utils.py:325-334 -> (latent, latents): `latent` [1, C, height/8, width/8] drawn on the CPU from `generator` when None (the
+    draw is the reference's, whatever device the model is on), `latents` = the same on `model.device`."""
+    shape = (1, _in_channels(model.unet), height // 8, width // 8)
+    if latent is None:
+        latent = torch.randn(shape, generator=generator)
+    latents = latent.expand(*shape).to(model.device)
+    return latent, latents
+
+
+def latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True):
+    """ptp_utils.py:337-349: one sampling step.  As in the reference's `low_resource` branch the prediction is the conditional
+    one alone -- `context[1]`, the learned embedding; `context[0]` and `guidance_scale` are unused (the reference has the
+    guidance line commented out).  The batched two-context branch is not built (classifier-free guidance is out of scope)."""
+    if not low_resource:
+        raise NotImplementedError("latent_step: only the low_resource branch (conditional prediction alone) is built")
+    noise_pred = _unet_forward_shared_context(model, latents, t, context[1])
+    latents = model.scheduler.step(noise_pred, t, latents)["prev_sample"]
+    if controller is not None:
+        latents = controller.step_callback(latents)
+    return latents
+
+
+@torch.no_grad()
+def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int = 50, guidance_scale: float = 7.5,
+                          generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
+                          height: int = 512, width: int = 512, output_type: str = "uint8"):
+    """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` deterministic DDIM
+    steps and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
+    tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
+    noise [1, C, height/8, width/8] on the CPU (given, or drawn from `generator` on the CPU as the reference draws it).
+
+    Like the reference's `low_resource=True` branch only the learned embedding conditions the UNet: no unconditional pass, no
+    text encoder, `guidance_scale` unused.  NOT reproduced: the reference's `torch.load` of two hard-coded files
+    ("example_attn_maps_indices.pt", "outputs/indices.pt", whose contents it never uses) and
+    `register_attention_control_generation`, which re-installs the attention math the module tree already computes.  `height`,
+    `width` and `output_type` are keyword-only extensions (the reference fixes 512 x 512).  The scheduler's timestep table is
+    restored afterwards, so a sampling call between optimisation steps does not move their noise level.  The model must have
+    been loaded with its VAE decoder (`load_ldm(..., decoder=True)`)."""
+    if output_type not in ("uint8", "float"):
+        raise ValueError(f"output_type must be 'uint8' or 'float', got {output_type!r}")
+    vae = model.vae.module if isinstance(model.vae, torch.nn.DataParallel) else model.vae
+    if not getattr(vae, "has_decoder", False):
+        raise RuntimeError("text2image_ldm_stable: this model was loaded without the VAE decoder; load it with "
+                           "optimize_token.load_ldm(..., decoder=True)")
+    if height % 8 or width % 8:
+        raise ValueError("height and width must be multiples of 8")
+    latent, latents = init_latent(latent, model, height, width, generator)
+    latents = latents.to(torch.float32).contiguous()
+    embedding = embedding.to(device=model.device, dtype=torch.float32)
+    context = [None, embedding]
+    sched = model.scheduler
+    kept = (sched.timesteps, sched.num_inference_steps)
+    sched.set_timesteps(num_inference_steps)
+    try:
+        with ops.up2_in_unet(latents.is_cuda):
+            for t in sched.timesteps:
+                latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)
+                if controller is not None:
+                    controller.reset()
+    finally:
+        sched.timesteps, sched.num_inference_steps = kept
+    if output_type == "float":
+        return _latent2float(vae, latents), latent
+    return latent2image(vae, latents), latent
 
 
 # ---------------------------------------------------------------------------------------------

@@ -41,7 +41,11 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # their input gradient (ops.Conv3x3Fn.backward); the zero-stuffed stride-2 gradient runs on the same kernels and counts here too
     "conv3x3.bwd_data": dict(_WINO),
     "conv_in": {"small": "hip"},                          # <= 4 input channels, forward only (ops.conv3x3_small)
-    "conv_out": {"lib": "library"},                       # <= 8 output channels: below the Winograd kernels' channel blocks
+    # <= 8 output channels: below the Winograd kernels' channel blocks; the VAE decoder's <= 4 on its own VALU kernel
+    "conv_out": {"lib": "library", "small_out": "hip"},
+    # Upsample2D of the VAE decoder, and of the UNet inside the sampling loop (ops.conv3x3_up2): polyphase kernel on the
+    # low-resolution input / interpolate + the stride-1 convolution (which notes its own `conv3x3` route as well)
+    "upsample_conv": {"up2_poly": "hip", "interp_wino": "hip"},
     "conv3x3_s2": {"s2_direct": "hip", "s2_wino": "hip"},  # ops._conv3x3_s2_raw: direct / polyphase Winograd F(4x4,2x2)
     "conv3x3_s2.bwd_data": {"zero_stuffed": "hip", "lib": "library"},
     "downsample": {"s2_direct": "hip", "eager": "eager"},
@@ -55,6 +59,7 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "add_layer_norm": {"add_ln": "hip"},
     "vae.attention": {"lib_core": "library", "eager": "eager"},
     "vae.tail": {"composed": "hip", "eager": "eager"},
+    "vae.decoder": dict(_BLOCK),                          # Decoder.forward: fused tail (GroupNorm + SiLU, small-output conv_out) / its own
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),
