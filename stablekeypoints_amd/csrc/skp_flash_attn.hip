@@ -882,6 +882,18 @@ __global__ __launch_bounds__(64 * NW, MINB) void skp_fa2_bwd_fused_kernel(const 
         fa2_colacc<D, NQ, TT>(Qs, dp, dka, i16, g);               // dK^T[c][t] += sum_n Q[n][c] dS[n][t]
         // dS -> LDS, [query n][key of the block]
         if (OVL) __syncthreads();                              // the exchange buffer lies over Q | dO: everyone is done reading them
+        if (OVL && t0 + X::KB > Nk) {
+            // ragged last key block: a missing key scores 0 against the zero rows of the LDS copy, so its P = exp2(-lse2) is
+            // +inf once lse2 < -128 (every logit of the row far below 0), and inf * 0 would reach dQ through those zero rows
+            // (its dK / dV columns are never stored)
+            const int left = Nk - t0 - KW * wave;               // keys of this wave that exist (wave-uniform)
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt)
+                if (16 * tt + (int)(threadIdx.x & 15) >= left) {
+#pragma unroll
+                    for (int nt = 0; nt < NQ; ++nt) dp[nt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
 #pragma unroll
         for (int nt = 0; nt < NQ; ++nt)
 #pragma unroll
