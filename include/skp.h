@@ -250,6 +250,18 @@ int skp_flash_attn_bwd_split_ld_f32(const float* q, const float* k, const float*
                                     const float* lse, float* dq, float* dk, float* dv, void* workspace, int B, int Bk, int H,
                                     int N, int Nk, int d, float scale, int ldg, void* stream);
 
+/* The flash-attention FORWARD for one WIDE head, d = 512 (skp_flash_attn_wide.hip; the VAE mid-block's AttentionBlock):
+ * out [B,N,H*512] = softmax(scale q k^T) v per head, head h = channels [512h, 512h + 512) of q [B,N,H*512], k / v [Bk,Nk,H*512].
+ * fp32 in / out, exact fp32 products (v_mfma_f32_16x16x4_f32), fp32 online softmax over 16-key tiles; the scores are never
+ * written to memory and there is no lse output (no backward exists for this head size).  q, k, v, out 16-byte aligned.
+ * _ok: 1 iff d == 512, Bk == B and every size > 0 (and one batch row of k / v stays below 2 GiB, the 64-query workgroup count
+ * below 2^31).  _workspace: bytes the launch wants in `workspace`; 0 today (no key-range split is planned for any shape:
+ * `workspace` may then be NULL), < 0 for a shape _ok refuses.  It never grows with N * Nk. */
+int skp_flash_attn_fwd_wide_ok(int B, int Bk, int H, int N, int Nk, int d);
+int64_t skp_flash_attn_fwd_wide_workspace(int B, int Bk, int H, int N, int Nk, int d);
+int skp_flash_attn_fwd_wide_f32(const float* q, const float* k, const float* v, float* out, void* workspace,
+                                int B, int Bk, int H, int N, int Nk, int d, float scale, void* stream);
+
 /* Flash-style self-attention (ptp_utils.py:493-506 with context = x) for the long image-token sequences: fp32 MFMA,
  * 64-key tiles in LDS, online softmax; the [B*h,N,N] scores are never materialised.
  * q, k, v, out: [B,N,H*d]; lse: [B,H,N] (natural log).  Limits: d in {8,16,32,40,64,80,160}. */

@@ -140,19 +140,24 @@ def _block_forward(m: BasicTransformerBlock):
 
 def _vae_attention_forward(m: AttentionBlock):
     """VAE mid-block attention: GroupNorm on the fused kernel, tiled NCHW -> token transpose instead of a strided copy, the
-    way back fused with the residual add.  The d = 512 single-head core stays on the library GEMMs + softmax."""
+    way back fused with the residual add.  The d = 512 single-head core: the wide flash kernel or the library GEMMs + softmax,
+    as `ops.vae_attn_route` says (the kernel has no backward)."""
     orig = m.forward
 
     def forward(x):
         if not (ops.group_norm_supported(x, m.group_norm.num_groups) and ops.layout_supported(x)):
             routes.note("vae.attention", "eager")
             return orig(x)
-        routes.note("vae.attention", "lib_core")
         b, c, hh, ww = x.shape
-        t = ops.nchw_to_tokens(ops.group_norm_silu(x, m.group_norm, silu=False))        # [b, hh*ww, c]
-        q, k, v = m.query(t), m.key(t), m.value(t)
         nh = m.num_heads
         d = c // nh
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in m.parameters()))
+        route = ops.vae_attn_route(b, nh, hh * ww, d, needs_grad)
+        routes.note("vae.attention", route)
+        t = ops.nchw_to_tokens(ops.group_norm_silu(x, m.group_norm, silu=False))        # [b, hh*ww, c]
+        q, k, v = m.query(t), m.key(t), m.value(t)
+        if route == "flash_wide":
+            return ops.tokens_to_nchw_add(m.proj_attn(ops.flash_attn_wide(q, k, v, nh, 1.0 / (d ** 0.5))), x)
 
         def split(u):
             return u.reshape(b, -1, nh, d).permute(0, 2, 1, 3).reshape(b * nh, -1, d)

@@ -886,6 +886,48 @@ def self_attention(q, k, v, heads: int, scale: float):
     return FlashAttnFn.apply(q, k, v, int(heads), float(scale))
 
 
+# ---------------------------------------------------------------------------------------------
+# VAE mid-block attention: one head of d = 512 (csrc/skp_flash_attn_wide.hip, forward only)
+# ---------------------------------------------------------------------------------------------
+# "auto": the flash kernel from VAE_FLASH_MIN_KEYS keys on, the library GEMMs + softmax below it; "flash": the kernel wherever it
+# can run; "lib": the library everywhere.  Measured (profiles/vae_attention.md), the kernel is 1.16-2.07x SLOWER than the library
+# at 9 216 and 16 384 keys, so in "auto" the route exists for memory, not speed: it opens where the library's two fp32 score
+# matrices of ONE row (8 keys^2 bytes) exceed 8 GiB, i.e. above 32 768 keys.  The 512^2 encode / decode (4 096 keys) and SD-2.1 /
+# SDXL (9 216 / 16 384) stay on the library.
+VAE_ATTN_MODE = "auto"
+VAE_FLASH_MIN_KEYS = 32 * 1024 + 1
+VAE_ATTN_MODES = ("auto", "flash", "lib")
+
+
+def vae_attn_route(B: int, heads: int, n_keys: int, d: int, needs_grad: bool) -> str:
+    """Route of the `vae.attention` core for self-attention over n_keys tokens, `heads` heads of d channels: "flash_wide" or
+    "lib_core".  A pure function of its arguments and the two module attributes; the kernel has no backward, so an input that
+    needs a gradient always takes the library."""
+    if VAE_ATTN_MODE not in VAE_ATTN_MODES:
+        raise ValueError(f"ops.VAE_ATTN_MODE must be one of {VAE_ATTN_MODES}, got {VAE_ATTN_MODE!r}")
+    if VAE_ATTN_MODE == "lib" or needs_grad:
+        return "lib_core"
+    if VAE_ATTN_MODE == "auto" and n_keys < VAE_FLASH_MIN_KEYS:
+        return "lib_core"
+    return "flash_wide" if N.lib().skp_flash_attn_fwd_wide_ok(B, B, heads, n_keys, n_keys, d) == 1 else "lib_core"
+
+
+def flash_attn_wide(q, k, v, heads: int, scale: float):
+    """Direct entry (tests / tools, and the flash route of the VAE attention): out = softmax(scale q k^T) v per head of 512
+    channels, q [B,N,heads*512], k / v [B,Nk,heads*512]; no gradient."""
+    q, k, v = _dev(q, "q"), _dev(k, "k"), _dev(v, "v")
+    B, Nq, C = q.shape
+    Bk, Nk, Ck = k.shape
+    if C % heads or Ck != C or v.shape != k.shape:
+        raise RuntimeError(f"flash_attn_wide: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, {heads} heads")
+    shape = (B, Bk, heads, Nq, Nk, C // heads)
+    out = torch.empty_like(q)
+    ws = _workspace("skp_flash_attn_fwd_wide_workspace", *shape, device=q.device)
+    N.check(N.lib().skp_flash_attn_fwd_wide_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(ws), *shape,
+                                                float(scale), _stream()), "skp_flash_attn_fwd_wide_f32")
+    return out
+
+
 class AddBiasResidualFn(torch.autograd.Function):
     """out = a + b + bias[None,:,None,None] in one pass (bias frozen); gradients pass straight through."""
 

@@ -57,7 +57,8 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "group_norm": {"gn_fold": "hip", "gn_apply": "hip"},  # folded into the consuming convolution's patch load / own apply pass
     "group_norm.stats": {"producer_blocks": "hip", "own_pass": "hip"},
     "add_layer_norm": {"add_ln": "hip"},
-    "vae.attention": {"lib_core": "library", "eager": "eager"},
+    # VAE mid-block attention, one head of d = 512 (ops.vae_attn_route): the wide flash forward / library GEMMs + softmax
+    "vae.attention": {"flash_wide": "hip", "lib_core": "library", "eager": "eager"},
     "vae.tail": {"composed": "hip", "eager": "eager"},
     "vae.decoder": dict(_BLOCK),                          # Decoder.forward: fused tail (GroupNorm + SiLU, small-output conv_out) / its own
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
@@ -73,7 +74,8 @@ ROUTES: Dict[str, Dict[str, str]] = {
 
 # The non-HIP routes the supported configurations are MEANT to take on the GPU today: (site, route) -> reason.
 DOCUMENTED_LIBRARY_ROUTES: Dict[Tuple[str, str], str] = {
-    ("vae.attention", "lib_core"): "VAE mid-block attention, one head of d = 512: baddbmm + softmax + bmm (no flash kernel at that head size)",
+    ("vae.attention", "lib_core"): "VAE mid-block attention, one head of d = 512, below ops.VAE_FLASH_MIN_KEYS keys (32 769; the 512^2 encode / decode has 4 096, SDXL at 1024^2 16 384) or with an "
+                                    "input that needs a gradient: baddbmm + softmax + bmm (the wide flash kernel is forward only)",
     ("conv_out", "lib"): "UNet conv_out 320 -> 4 (full forward only) and a VAE conv_out 512 -> 8 whose tail is not composed: "
                          "output channels below the Winograd kernels' 32-channel blocks",
     ("downsample.untiled", "eager"): "Downsample2D whose input is no multiple of the stride-2 kernel's 16 x 32 pixel tile (SD-1.5 at 512^2: "
