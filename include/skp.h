@@ -24,6 +24,10 @@
  *   skp_losses_fwd_f32                      optimize.py:157-206, optimize_token.py:203-241,
  *                                           invertable_transform.py:72-92
  *   skp_rows_axpy_f32                       autograd scatter of the loss gradients into [T,R,R]
+ *   skp_conv3x3_up2_f32 / skp_conv3x3_small_out_f32   Upsample2D and conv_out of image sampling (ptp_utils.py:316-322)
+ *   skp_axpby_f32 / skp_ddim_step_f32       the scheduler step of ptp_utils.py:337-349 (plain / guided, epsilon, v or sample
+ *                                           prediction, optional clamp, optional second copy of the result)
+ *   skp_image_u8_nhwc_f32                   ptp_utils.py:320-322 (float NCHW image -> uint8 NHWC)
  */
 #ifndef SKP_H
 #define SKP_H
@@ -430,6 +434,27 @@ int skp_conv3x3_small_out_f32(const void* x, const void* w, const void* bias, vo
 /* y[i] = a * x[i] + b * z[i] for i < n (y may alias x or z): the eta = 0 DDIM update x_prev = c1 x_t + c2 eps with the two
  * coefficients computed on the host (ldm/scheduler.py DDIMScheduler.step). */
 int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, float b, void* stream);
+
+/* The guided DDIM update of the sampling loop in one pass (skp_ddim_step.hip; ldm/scheduler.py DDIMScheduler.step with
+ * `uncond_output`, a prediction type other than epsilon, or clipping).  Per element i < n:
+ *   m         = m_u ? m_u + guidance * (m_c - m_u) : m_c                 (classifier-free guidance; m_u may be NULL)
+ *   (x0, eps) = prediction 0 (epsilon): ((x - sb m) / sa, m)
+ *               prediction 1 (v):       (sa x - sb m, sa m + sb x)
+ *               prediction 2 (sample):  (m, (x - sa m) / sb)
+ *   x0        = clamp(x0, -1, 1) if clip        (eps stays as derived before the clamp)
+ *   y         = pa x0 + pb eps
+ * sa, sb, pa, pb = sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev), computed by the host in fp64 and rounded once.
+ * y holds copies * n floats: the result at y[0..n) and, with copies == 2, again at y[n..2n) (the duplicated UNet input of the next
+ * guided step).  y may alias x; with copies == 2, x may be the first copy.  16-byte accesses when x, m_c, m_u and y are 16-byte
+ * aligned (the second copy too when n % 4 == 0), scalar accesses otherwise; any n.  No atomics: bit-identical from call to call.
+ * SKP_E_BADARG: x / m_c / y NULL, n <= 0, copies outside {1, 2}, prediction outside {0, 1, 2}. */
+int skp_ddim_step_f32(const float* x, const float* m_c, const float* m_u, float* y, int64_t n, int copies, float guidance,
+                      int prediction, float sa, float sb, float pa, float pb, int clip, void* stream);
+
+/* Image to bytes (ptp_utils.py `latent2image`): x float [B,3,H,W] in [0, 1] (the decoder's image epilogue) -> y uint8 [B,H,W,3],
+ * y = (unsigned char)(x * 255.0f), truncating, no clamp: exactly what the host expression (x.permute(0,2,3,1) * 255).astype(uint8)
+ * gives.  Any H, W (four pixels per lane when H * W % 4 == 0, one otherwise). */
+int skp_image_u8_nhwc_f32(const float* x, unsigned char* y, int B, int H, int W, void* stream);
 
 /* GEGLU of the transformer feed-forward (diffusers attention.GEGLU [third party], inside the hooked UNet forward):
  *   y[r, c] = p[r, c] * gelu(p[r, inner + c])    p: [rows, 2*inner], y: [rows, inner], exact (erf) gelu, inner % 4 == 0

@@ -99,6 +99,8 @@ SIGNATURES = {
     "skp_conv3x3_up2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_small_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "skp_axpby_f32": [_vp, _vp, _vp, _i64, _f, _f, _vp],
+    "skp_ddim_step_f32": [_vp, _vp, _vp, _vp, _i64, _i, _f, _i, _f, _f, _f, _f, _i, _vp],
+    "skp_image_u8_nhwc_f32": [_vp, _vp, _i, _i, _i, _vp],
     "skp_conv3x3_f4_stats_blocks": [_i, _i, _i, _i, _i],
     "skp_conv3x3_f4_stats_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_s2_stats_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

@@ -1430,6 +1430,46 @@ def axpby(x, z, a: float, b: float):
     return y
 
 
+DDIM_PREDICTION = {"epsilon": 0, "v_prediction": 1, "sample": 2}
+
+
+def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, guidance: float = 1.0, prediction="epsilon",
+              clip: bool = False, copies: int = 1, out=None):
+    """The guided DDIM update in one pass (csrc/skp_ddim_step.hip, formula in include/skp.h): m = m_u + guidance (m_c - m_u) when
+    `m_u` is given, else m_c; (x0, eps) from (x, m) by `prediction` ("epsilon" | "v_prediction" | "sample" or 0 | 1 | 2); x0
+    clamped to [-1, 1] when `clip`; y = pa x0 + pb eps.  -> y shaped like x, or with `copies=2` like torch.cat([x, x]): the result
+    twice along dim 0.  `out`: a contiguous float32 tensor of copies * x.numel() elements to write into; it may be x itself, or
+    (copies = 2) a buffer whose first half x is."""
+    x, m_c = _dev(x, "x"), _dev(m_c, "m_c")
+    m_u = _dev(m_u, "m_u") if m_u is not None else None
+    if m_c.shape != x.shape or (m_u is not None and m_u.shape != x.shape):
+        raise RuntimeError("ddim_step: shapes differ")
+    pred = DDIM_PREDICTION.get(prediction, prediction)
+    if pred not in (0, 1, 2) or copies not in (1, 2):
+        raise ValueError(f"ddim_step: prediction {prediction!r} / copies {copies!r}")
+    n = x.numel()
+    if out is None:
+        out = torch.empty((copies * x.shape[0],) + tuple(x.shape[1:]) if x.dim() else (copies,), device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == copies * n):
+        raise RuntimeError("ddim_step: `out` must be a contiguous float32 device tensor of copies * x.numel() elements")
+    N.check(N.lib().skp_ddim_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), out.data_ptr(), n, int(copies), float(guidance),
+                                      int(pred), float(sa), float(sb), float(pa), float(pb), int(bool(clip)), _stream()),
+            "skp_ddim_step_f32")
+    return out
+
+
+def image_u8_nhwc(x):
+    """float [B,3,H,W] in [0, 1] -> uint8 [B,H,W,3] = (x.permute(0, 2, 3, 1) * 255) truncated, on the device
+    (csrc/skp_ddim_step.hip; `ptp_utils.latent2image`)."""
+    x = _dev(x.detach(), "x")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"image_u8_nhwc: expected [B,3,H,W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    y = torch.empty(B, H, W, 3, device=x.device, dtype=torch.uint8)
+    N.check(N.lib().skp_image_u8_nhwc_f32(x.data_ptr(), y.data_ptr(), B, H, W, _stream()), "skp_image_u8_nhwc_f32")
+    return y
+
+
 def mfma_issue_rate(waves_per_simd: int = 1, iters: int = 20000, device=None) -> float:
     """Measurement aid: TFLOP/s of back-to-back independent fp32 MFMAs with `waves_per_simd` waves on every SIMD."""
     import ctypes

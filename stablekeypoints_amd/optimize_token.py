@@ -8,6 +8,9 @@ PROCESS drives (1).  The data-parallel width comes from `torch.distributed.get_w
 """
 from __future__ import annotations
 
+import json
+import os
+
 import torch
 
 from . import ptp_utils
@@ -16,12 +19,21 @@ from .ldm.scheduler import DDIMScheduler
 
 
 def load_ldm(device, type="CompVis/stable-diffusion-v1-4", feature_upsample_res=256, my_token=None,
-             init_on_device=False, decoder=False):
+             init_on_device=False, decoder=False, prediction_type=None):
     """optimize_token.py:24-78.  `init_on_device` (extension, synthetic weights only): draw the seeded weights directly
     on `device` instead of on the host (multi-GPU start-up; see StableDiffusionPipeline.build).  `decoder` (extension): also
-    build / load the VAE's decoder half, which only image sampling needs (ptp_utils.text2image_ldm_stable)."""
+    build / load the VAE's decoder half, which only image sampling needs (ptp_utils.text2image_ldm_stable).  `prediction_type`
+    (extension): what the UNet predicts, "epsilon" | "v_prediction" | "sample"; None reads it from
+    `<checkpoint dir>/scheduler/scheduler_config.json` when `type` is a directory that has one (Stable Diffusion 2.1 at 768^2 is a
+    v-prediction model), else "epsilon" -- synthetic architectures included.  Only `scheduler.step` (image sampling) reads it."""
+    if prediction_type is None:
+        prediction_type = "epsilon"
+        cfg = os.path.join(str(type), "scheduler", "scheduler_config.json")
+        if os.path.isdir(str(type)) and os.path.isfile(cfg):      # (a directory is a checkpoint to from_pretrained too, whatever its name)
+            with open(cfg) as f:
+                prediction_type = json.load(f).get("prediction_type") or "epsilon"
     scheduler = DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                              clip_sample=False, set_alpha_to_one=False)
+                              clip_sample=False, set_alpha_to_one=False, prediction_type=prediction_type)
     scheduler.set_timesteps(50)                                   # NUM_DDIM_STEPS, optimize_token.py:33-34
     ldm = StableDiffusionPipeline.from_pretrained(type, use_auth_token=my_token, scheduler=scheduler,
                                                   init_device=device if init_on_device else None,

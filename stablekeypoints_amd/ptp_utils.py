@@ -3,7 +3,8 @@
 Kept names/signatures: `AttentionControl`, `AttentionStore`,
 `register_attention_control`, `find_pred_noise`, `run_and_find_attn`, `image2latent`,
 `find_top_k_gaussian`, `furthest_point_sampling`, `init_random_noise`, and the image-sampling entries `diffusion_step`,
-`latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461).
+`latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461); `init_latents` and
+`guided_latent_step` are this port's batched / classifier-free-guidance companions of the last two.
 
 What changes under the hood
   * the hooked cross-attention does NOT up-sample the layer input, re-project it and materialise a
@@ -18,6 +19,7 @@ What changes under the hood
 from __future__ import annotations
 
 import abc
+import contextlib
 from typing import Optional
 
 import numpy as np
@@ -378,6 +380,16 @@ def latent2image(vae, latents):
     [0, 1] map is the epilogue of the decoder's last convolution.)"""
     with torch.no_grad():
         image = _latent2float(vae, latents)
+    return _image2uint8(image)
+
+
+def _image2uint8(image):
+    """float [B, 3, H, W] in [0, 1] -> uint8 numpy [B, H, W, 3], truncating.  A float32 device image is permuted and converted by
+    one kernel (csrc/skp_ddim_step.hip), so the copy to the host is bytes; the result is the host expression's, bit for bit."""
+    if image.is_cuda and image.dtype == torch.float32:
+        routes.note("image.u8", "nhwc_u8")
+        return ops.image_u8_nhwc(image).cpu().numpy()
+    routes.note("image.u8", "host")
     image = image.cpu().permute(0, 2, 3, 1).numpy()
     return (image * 255).astype(np.uint8)
 
@@ -401,6 +413,58 @@ def init_latent(latent, model, height, width, generator):
     return latent, latents
 
 
+def init_latents(latent, model, height, width, generators):
+    """`init_latent` for n images -> (latent [n, C, height/8, width/8] on the CPU, the same on `model.device`).  `generators` is a list:
+    image i is drawn as torch.randn((1, C, h, w), generator=generators[i]) on the CPU -- the reference's draw, so image i of a batch
+    starts from the noise the single-image call with that generator starts from.  A given `latent` [n, C, h, w] is used as it is
+    (`generators` is then not read)."""
+    shape = (1, _in_channels(model.unet), height // 8, width // 8)
+    if latent is None:
+        if not generators:
+            raise ValueError("init_latents: a list of generators (one per image) or a latent [n, C, h, w]")
+        latent = torch.cat([torch.randn(shape, generator=g) for g in generators])
+    if latent.dim() != 4 or tuple(latent.shape[1:]) != shape[1:]:
+        raise ValueError(f"init_latents: latent {tuple(latent.shape)} is not [n, {shape[1]}, {shape[2]}, {shape[3]}]")
+    return latent, latent.to(model.device)
+
+
+def guided_latent_step(model, controller, latents, context, t, guidance_scale, *, doubled=False):
+    """One sampling step with classifier-free guidance: the branch of ptp_utils.py:337-349 that the reference's `low_resource=False`
+    names, as an entry of its own (`latent_step` stays the conditional prediction alone).  `context = [uncond, cond]`, each [1, T, D];
+    `latents` [n, C, h, w].
+      * equal T: ONE UNet forward of 2n rows, the unconditional rows first, context [2n, T, D] (every layer projects it per row, as
+        for any per-row context); the two halves of the output are the unconditional and the conditional prediction;
+      * different T (a 77-token unconditional embedding against a 500-token learned one): two forwards of n rows, each with its
+        shared context row.
+    Both end in one `scheduler.step(cond, t, latents, uncond_output=uncond, guidance_scale=...)` -- on the GPU one kernel that mixes
+    the two predictions and applies the update -- followed by `controller.step_callback`, as in `latent_step`.
+    `doubled` (equal T only): `latents` is [2n, C, h, w] holding the n rows twice, and so is the result: the step writes its output
+    twice, so the loop of `text2image_ldm_stable` concatenates once before its first step and never after (GPU, equal T; the
+    host route and contexts of different length concatenate or run two forwards per step).  Works in whatever dtype the module tree and its inputs have."""
+    uncond, cond = context
+    same_t = uncond.shape[1] == cond.shape[1]
+    if doubled and not same_t:
+        raise ValueError("guided_latent_step: doubled latents need contexts of equal length")
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    if same_t:
+        rows = latents if doubled else torch.cat([latents, latents])
+        ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
+        pred = _unet_forward_shared_context(model, rows, t, ctx)
+        pred_u, pred_c = pred[:n], pred[n:]
+        latents = rows[:n]
+    else:
+        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
+        pred_c = _unet_forward_shared_context(model, latents, t, cond)
+    out = model.scheduler.step(pred_c, t, latents, uncond_output=pred_u, guidance_scale=guidance_scale,
+                               copies=2 if doubled else 1)["prev_sample"]
+    if controller is not None:
+        first = out[:n] if doubled else out
+        called = controller.step_callback(first)
+        if called is not first:
+            out = torch.cat([called, called]) if doubled else called
+    return out
+
+
 def latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True):
     """ptp_utils.py:337-349: one sampling step.  As in the reference's `low_resource` branch the prediction is the conditional
     one alone -- `context[1]`, the learned embedding; `context[0]` and `guidance_scale` are unused (the reference has the
@@ -414,17 +478,42 @@ def latent_step(model, controller, latents, context, t, guidance_scale, low_reso
     return latents
 
 
+@contextlib.contextmanager
+def _reproducible_library_convolutions():
+    """Inside the block the library convolutions that the sampling path still reaches (few-tile layers, `conv3x3` / `lib`) may
+    only use solvers that sum in a fixed order: a single-row 8^2 / 1^2 layer is otherwise split over its input channels with
+    atomic adds, and two calls with the same latent differ in the last bits.  The project's own kernels have no atomics on this
+    path.  This is a change of the existing default call too: its library convolutions may run on other solvers than before, so
+    its image can differ from earlier versions' in the last bits (and is the same from call to call).  The flag is process-wide
+    and the caller's again afterwards; like the scheduler's timestep table, which this call also borrows, it is not safe against
+    another thread running library convolutions or sampling on the same process at the same time."""
+    prev = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = prev
+
+
 @torch.no_grad()
 def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                           generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
-                          height: int = 512, width: int = 512, output_type: str = "uint8"):
+                          height: int = 512, width: int = 512, output_type: str = "uint8",
+                          uncond_embedding: Optional[torch.Tensor] = None):
     """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` deterministic DDIM
     steps and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
     noise [1, C, height/8, width/8] on the CPU (given, or drawn from `generator` on the CPU as the reference draws it).
 
-    Like the reference's `low_resource=True` branch only the learned embedding conditions the UNet: no unconditional pass, no
-    text encoder, `guidance_scale` unused.  NOT reproduced: the reference's `torch.load` of two hard-coded files
+    Batches: `generator` may be a list of n generators and `latent` may be [n, C, h, w]; all n images then go through every UNet
+    forward and the decoder together, `image` and `latent` have n rows, and image i starts from the noise the single-image call
+    with `generator[i]` starts from (`init_latents`).
+
+    `uncond_embedding` None (the default): like the reference's `low_resource=True` branch only the learned embedding conditions
+    the UNet -- no unconditional pass, no text encoder, `guidance_scale` unused.  `uncond_embedding` [1, T', D] (keyword-only
+    extension): classifier-free guidance of strength `guidance_scale` against it, `guided_latent_step`; T' may differ from T.
+    What the UNet predicts (epsilon, v, sample) is the scheduler's `prediction_type` (`load_ldm(..., prediction_type=)`).
+    The loop is not captured into a graph, eta is 0, DDIM is the only scheduler.  NOT reproduced: the reference's `torch.load` of two hard-coded files
     ("example_attn_maps_indices.pt", "outputs/indices.pt", whose contents it never uses) and
     `register_attention_control_generation`, which re-installs the attention math the module tree already computes.  `height`,
     `width` and `output_type` are keyword-only extensions (the reference fixes 512 x 512).  The scheduler's timestep table is
@@ -438,24 +527,47 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                            "optimize_token.load_ldm(..., decoder=True)")
     if height % 8 or width % 8:
         raise ValueError("height and width must be multiples of 8")
-    latent, latents = init_latent(latent, model, height, width, generator)
+    if isinstance(generator, (list, tuple)) or (latent is not None and latent.dim() == 4 and latent.shape[0] != 1):
+        if isinstance(generator, (list, tuple)) and latent is not None and len(generator) != latent.shape[0]:
+            raise ValueError(f"{len(generator)} generators for a latent of {latent.shape[0]} rows (a given latent is used as it is; "
+                             "pass generator=None with it, or one generator per row)")
+        latent, latents = init_latents(latent, model, height, width, generator)
+    else:
+        latent, latents = init_latent(latent, model, height, width, generator)
     latents = latents.to(torch.float32).contiguous()
+    n = latents.shape[0]
     embedding = embedding.to(device=model.device, dtype=torch.float32)
-    context = [None, embedding]
+    guided = uncond_embedding is not None
+    if guided:
+        uncond = uncond_embedding.to(device=model.device, dtype=torch.float32)
+        uncond = uncond[None] if uncond.dim() == 2 else uncond
+        if uncond.dim() != 3 or uncond.shape[0] != 1 or uncond.shape[-1] != embedding.shape[-1]:
+            raise ValueError(f"uncond_embedding {tuple(uncond_embedding.shape)} must be [1, T, {embedding.shape[-1]}]")
+    context = [uncond if guided else None, embedding]
+    # on the GPU a guided step with contexts of equal length keeps the 2n-row UNet input between steps (written by the step kernel)
+    doubled = guided and latents.is_cuda and uncond.shape[1] == embedding.shape[1]
+    if doubled:
+        latents = torch.cat([latents, latents])
     sched = model.scheduler
     kept = (sched.timesteps, sched.num_inference_steps)
-    sched.set_timesteps(num_inference_steps)
-    try:
-        with ops.up2_in_unet(latents.is_cuda):
-            for t in sched.timesteps:
-                latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)
-                if controller is not None:
-                    controller.reset()
-    finally:
-        sched.timesteps, sched.num_inference_steps = kept
-    if output_type == "float":
-        return _latent2float(vae, latents), latent
-    return latent2image(vae, latents), latent
+    with _reproducible_library_convolutions():                 # the loop and the decode: one call, one result, bit for bit
+        sched.set_timesteps(num_inference_steps)
+        try:
+            with ops.up2_in_unet(latents.is_cuda):
+                for t in sched.timesteps:
+                    if guided:
+                        latents = guided_latent_step(model, controller, latents, context, t, guidance_scale, doubled=doubled)
+                    else:
+                        latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)
+                    if controller is not None:
+                        controller.reset()
+        finally:
+            sched.timesteps, sched.num_inference_steps = kept
+        if doubled:
+            latents = latents[:n]
+        if output_type == "float":
+            return _latent2float(vae, latents), latent
+        return latent2image(vae, latents), latent
 
 
 # ---------------------------------------------------------------------------------------------

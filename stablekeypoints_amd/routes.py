@@ -61,6 +61,8 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "vae.attention": {"flash_wide": "hip", "lib_core": "library", "eager": "eager"},
     "vae.tail": {"composed": "hip", "eager": "eager"},
     "vae.decoder": dict(_BLOCK),                          # Decoder.forward: fused tail (GroupNorm + SiLU, small-output conv_out) / its own
+    # ptp_utils.latent2image: float NCHW image -> uint8 NHWC on the device (bytes cross to the host) / numpy on the host
+    "image.u8": {"nhwc_u8": "hip", "host": "host"},
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),

@@ -3,9 +3,14 @@
 
     python tools/generate_image.py --model <checkpoint dir | synthetic-sd15 | tiny> --embedding emb.pt --out out/img
                                    [--steps 50] [--seed 0] [--n 1] [--size 512] [--device cuda]
+                                   [--uncond unc.pt --guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
 
 `--embedding`: a tensor [1, T, D] (or [T, D]) saved with torch.save -- what `optimize_embedding` returns.  Image i is sampled from
-seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3])."""
+seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3]).
+`--uncond`: a tensor saved the same way, the unconditional / negative embedding of classifier-free guidance with strength
+`--guidance` (its token count may differ from the embedding's); without it only the embedding conditions the UNet.
+`--batch B`: B images per sampling call (the seeds, the images' starting noise and the file names do not depend on it).
+`--prediction-type`: what the UNet predicts; default: the checkpoint's scheduler/scheduler_config.json, else epsilon."""
 import argparse
 import os
 import sys
@@ -24,6 +29,10 @@ def main():
     ap.add_argument("--n", type=int, default=1)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--uncond", default=None)
+    ap.add_argument("--guidance", type=float, default=7.5)
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--prediction-type", default=None, choices=("epsilon", "v_prediction", "sample"))
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -32,22 +41,32 @@ def main():
     emb = torch.load(a.embedding, map_location="cpu", weights_only=True)
     if emb.dim() == 2:
         emb = emb[None]
-    ldm, controllers, _ = load_ldm(a.device, a.model, decoder=True)
+    unc = None
+    if a.uncond is not None:
+        unc = torch.load(a.uncond, map_location="cpu", weights_only=True)
+        unc = unc[None] if unc.dim() == 2 else unc
+    if a.batch < 1:
+        ap.error("--batch must be at least 1")
+    ldm, controllers, _ = load_ldm(a.device, a.model, decoder=True, prediction_type=a.prediction_type)
     controller = next(iter(controllers.values()))
     try:
         from PIL import Image
     except ImportError:
         Image = None
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for i in range(a.n):
-        image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps,
-                                                   generator=torch.Generator().manual_seed(a.seed + i), height=a.size, width=a.size)
-        path = f"{a.out}_{i}" + (".png" if Image is not None else ".npy")
-        if Image is not None:
-            Image.fromarray(image[0]).save(path)
-        else:
-            np.save(path, image[0])
-        print(path)
+    for first in range(0, a.n, a.batch):
+        ids = range(first, min(first + a.batch, a.n))
+        gens = [torch.Generator().manual_seed(a.seed + i) for i in ids]
+        image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps, guidance_scale=a.guidance,
+                                                   generator=gens[0] if a.batch == 1 else gens, height=a.size, width=a.size,
+                                                   uncond_embedding=unc)
+        for row, i in enumerate(ids):
+            path = f"{a.out}_{i}" + (".png" if Image is not None else ".npy")
+            if Image is not None:
+                Image.fromarray(image[row]).save(path)
+            else:
+                np.save(path, image[row])
+            print(path)
 
 
 if __name__ == "__main__":
