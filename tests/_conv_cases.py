@@ -1,0 +1,572 @@
+"""Inputs, references, the error metric and the table of variants of the convolution-edge tests (test_conv_edges_host.py /
+_gpu.py).
+
+The operation under test is  y = conv2d(x, w, bias, stride 1 or 2, zero padding) (+ residual)  with a 3x3 filter, and its input
+gradient for a given dy.  Everything here runs on the CPU with plain torch ops:
+
+    make_input(family, shape, seed, seam)                      one fp32 activation of an input family
+    check_property(family, x, seam)                            the property that makes a family hard
+    case(variant, family)                                      inputs + fp64 reference + fp32 reference (kept, never modified)
+    plane_err(y, y64)                                          max over (b, c) of max|y - y64| / max|y64| within that plane
+    assert_conv_close(got, case, what)                         err <= M[kernel family] * err_fp32ref + 1e-7 per output
+
+The fp32 reference runs the SAME ALGORITHM as the kernel under test, in fp32 on the CPU: the Winograd kernels get an emulation
+with the transform matrices of csrc/skp_wino4_common.h (F(4x4,3x3), points 0, +-1, +-2) or of csrc/skp_conv_wino.hip
+(F(2x2,3x3)) -- filter transform, input transform, sum over channels, inverse transform -- the direct kernels get fp32
+F.conv2d.  A kernel's error is stated as a multiple of that reference's error on the same inputs.
+
+The launch plans of csrc/skp_conv_wino4.hip (wino4_use_c128 / wino4_grid / wino4_plan, wino4r_grid / wino4r_plan),
+csrc/skp_conv_wino.hip (wino_plan) and csrc/skp_conv_s2.hip (s2_splits) are restated at the end, beside
+`routes.wino4_form`, which restates the first of them for the route ledger; `assert_plan` checks every variant against the
+restatement AND against the library's own host queries.
+"""
+from __future__ import annotations
+
+import functools
+import math
+
+import torch
+import torch.nn.functional as F
+
+FAMILIES = ("randn", "post_silu", "dc", "outlier", "checker", "impulse")
+BIG_FAMILIES = ("randn", "outlier", "impulse")          # variants with more than 1000 tiles
+ABS_SLACK = 1e-7
+MIN_PLANE = 1e-2                                        # every fp64 plane maximum >= this x the global maximum
+
+# err_kernel <= M[kernel family] * err_fp32ref + ABS_SLACK: twice the largest ratio measured on the MI355X, rounded up, never above 8
+# (profiles/conv_edges.md holds the table these follow from: largest ratios 1.21, 1.81, 2.16, 1.68, 3.14, 1.18).
+M = {"f2": 3, "f4": 4, "f4r": 5, "gn": 4, "s2": 7, "small": 3}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# input families
+# ---------------------------------------------------------------------------------------------------------------------
+def impulse_sites(B, H, W, seam):
+    """(b, y, x) of the impulse family: four corners, four edges, both sides of a tile seam in x and in y, the last pixel of one
+    image and the first of the next, and one more in EVERY image."""
+    sy, sx = seam
+    sites = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1),
+             (0, 0, W // 2), (0, H - 1, W // 2), (0, H // 2, 0), (0, H // 2, W - 1)]
+    if sx < W:
+        sites += [(0, H // 2, sx - 1), (0, H // 2, sx)]
+    if sy < H:
+        sites += [(0, sy - 1, W // 2), (0, sy, W // 2)]
+    if B > 1:
+        sites += [(1, 0, 0)]                            # (0, H-1, W-1) is the last pixel of image 0
+    sites += [(b, (5 * b + 1) % H, (3 * b + 2) % W) for b in range(B)]
+    return list(dict.fromkeys(sites))
+
+
+def make_input(family, shape, seed, seam=(4, 4)):
+    assert family in FAMILIES
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, C, H, W, generator=g)
+    if family == "post_silu":
+        x = F.silu(2 * x + 0.7)
+    elif family == "dc":
+        x = x + 30
+    elif family == "outlier":
+        x[:, 3 % C] *= 1000
+    elif family == "checker":
+        sign = 1.0 - 2.0 * ((torch.arange(H)[:, None] + torch.arange(W)[None, :]) % 2)
+        x = 0.1 * x + sign
+    elif family == "impulse":
+        x.zero_()
+        for i, (b, yy, xx) in enumerate(impulse_sites(B, H, W, seam)):
+            x[b, i % C, yy, xx] = 1.0 + 0.25 * i
+    return x
+
+
+def check_property(family, x, seam=(4, 4)):
+    """-> (holds, what was measured) for one activation of `family`."""
+    B, C, H, W = x.shape
+    xd = x.double()
+    if family == "randn":
+        m = xd.mean().abs().item()                                # (four standard errors of the mean of n samples)
+        return m < 4 / math.sqrt(xd.numel()), f"|mean| {m:.3f}"
+    if family == "post_silu":
+        low = 1.0 - 4 * 1.43 / math.sqrt(xd.numel())              # silu(2 z + 0.7): mean 1.0, standard deviation 1.43
+        return xd.mean().item() > low and xd.min().item() > -0.28, f"mean {xd.mean().item():.2f} min {xd.min().item():.3f}"
+    if family == "dc":
+        return abs(xd.mean().item() - 30) < 0.5 and xd.std().item() < 1.5, f"mean {xd.mean().item():.2f} std {xd.std().item():.2f}"
+    if family == "outlier":
+        big = xd[:, 3 % C].abs().amax().item()
+        rest = xd[:, [c for c in range(C) if c != 3 % C]].abs().amax().item() if C > 1 else 0.0
+        return big > 100 * max(rest, 1e-30) or C == 1, f"channel {3 % C} max {big:.0f}, others {rest:.2f}"
+    if family == "checker":
+        sign = 1.0 - 2.0 * ((torch.arange(H)[:, None] + torch.arange(W)[None, :]) % 2).double()
+        a = (xd * sign).amin().item()
+        return a > 0.4, f"min of x * (-1)^(i+j) {a:.2f}"
+    sites = impulse_sites(B, H, W, seam)
+    nz = int((x != 0).sum())
+    per_image = (x != 0).flatten(1).any(1)
+    vals = x[x != 0]
+    ok = nz == len(sites) and bool(per_image.all()) and len(set(vals.tolist())) == nz
+    ok = ok and all(bool((x[b, :, yy, xx] != 0).any()) for b, yy, xx in sites)
+    return ok, f"{nz} impulses at {len(sites)} sites, every image hit: {bool(per_image.all())}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# references
+# ---------------------------------------------------------------------------------------------------------------------
+def backward_filter(w):
+    """Filter of the input gradient as a stride-1 convolution of dy: rotated by 180 degrees, channel roles swapped."""
+    return w.flip(2, 3).transpose(0, 1).contiguous()
+
+
+_W4 = {"BT": [[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
+              [0, 4, 0, -5, 0, 1]],
+       "G": [[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]],
+       "AT": [[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]]}
+_W2 = {"BT": [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]],
+       "G": [[1, 0, 0], [1 / 2, 1 / 2, 1 / 2], [1 / 2, -1 / 2, 1 / 2], [0, 0, 1]],
+       "AT": [[1, 1, 1, 0], [0, 1, -1, -1]]}
+
+
+def winograd_emulate(x, w, bias=None, residual=None, m=4, dtype=torch.float32):
+    """conv2d(x, w, padding 1) (+ bias + residual) as Winograd F(m x m, 3x3), every step in `dtype`: U = G w G^T,
+    V = B^T d B per (m+2)^2 patch, M = sum over channels of U * V per transform position, Y = A^T M A."""
+    mats = _W4 if m == 4 else _W2
+    BT, G, AT = (torch.tensor(mats[k], dtype=dtype) for k in ("BT", "G", "AT"))
+    B, C, H, W = x.shape
+    K, a = w.shape[0], m + 2
+    Hp, Wp = -(-H // m) * m, -(-W // m) * m                      # partial tiles: zero rows / columns, results cut off
+    xp = F.pad(x.to(dtype), (1, 1 + Wp - W, 1, 1 + Hp - H))
+    d = xp.unfold(2, a, m).unfold(3, a, m)                        # [B, C, th, tw, a, a]
+    th, tw = d.shape[2], d.shape[3]
+    V = BT @ d @ BT.T
+    U = G @ w.to(dtype) @ G.T                                     # [K, C, a, a]
+    Vp = V.permute(4, 5, 0, 2, 3, 1).reshape(a * a, B * th * tw, C)
+    Up = U.permute(2, 3, 1, 0).reshape(a * a, C, K)
+    Mm = torch.bmm(Vp, Up).reshape(a, a, B, th, tw, K).permute(2, 5, 3, 4, 0, 1)      # [B, K, th, tw, a, a]
+    Y = AT @ Mm @ AT.T                                            # [B, K, th, tw, m, m]
+    y = Y.permute(0, 1, 2, 4, 3, 5).reshape(B, K, Hp, Wp)[:, :, :H, :W]
+    if bias is not None:
+        y = y + bias.to(dtype)[None, :, None, None]
+    if residual is not None:
+        y = y + residual.to(dtype)
+    return y.contiguous()
+
+
+def conv_s2(x, w, bias, pad, dtype):
+    """The stride-2 convolution of Downsample2D: pad 0 = F.pad(x, (0,1,0,1)) + padding 0, pad 1 = padding 1."""
+    x = x.to(dtype)
+    if pad == 0:
+        x = F.pad(x, (0, 1, 0, 1))
+    return F.conv2d(x, w.to(dtype), None if bias is None else bias.to(dtype), stride=2, padding=pad)
+
+
+def zero_stuffed(dy, pad, H, W):
+    """dy of a stride-2 convolution on the input's grid (ops.ConvS2Fn.backward): its input gradient is the stride-1
+    backward-data convolution of this tensor."""
+    up = torch.zeros(dy.shape[0], dy.shape[1], H, W, dtype=dy.dtype)
+    o = 0 if pad == 1 else 1
+    up[:, :, o::2, o::2] = dy
+    return up
+
+
+def gn_silu(x, off, gamma, beta, groups, eps, dtype):
+    z = x.to(dtype)
+    if off is not None:
+        z = z + off.to(dtype)[:, :, None, None]
+    return F.silu(F.group_norm(z, groups, gamma.to(dtype), beta.to(dtype), eps))
+
+
+GN_GROUPS, GN_EPS = 32, 1e-6
+
+
+class Case:
+    """Inputs of one family for one variant with the fp64 and the fp32 reference of every output the variant produces."""
+
+    def __init__(self, v, family, seed=11):
+        self.v, self.family = v, family
+        B, ci, co, H, W = v["shape"]
+        kind = v["kind"]
+        g = torch.Generator().manual_seed(seed)
+        self.w = torch.randn(co, ci, 3, 3, generator=g) / (3 * math.sqrt(ci))
+        self.bias = torch.randn(co, generator=g) if v["bias"] else None
+        s2 = kind in ("s2", "s2_fn")
+        oh, ow = (H // 2, W // 2) if s2 else (H, W)
+        self.res = torch.randn(B, co, oh, ow, generator=g) if v["res"] else None
+        self.gamma = self.beta = self.off = None
+        if kind == "gn":
+            self.gamma = 1 + 0.3 * torch.randn(ci, generator=g)
+            self.beta = 0.3 * torch.randn(ci, generator=g)
+            self.off = torch.randn(B, ci, generator=g) if v["off"] else None
+        self.x = make_input(family, (B, ci, H, W), seed + 1, v["seam"])
+        self.dy = make_input(family, (B, co, oh, ow), seed + 2, v["seam_out"]) if v["bwd"] else None
+        self.ref64, self.ref32 = self._reference(torch.float64), self._reference(torch.float32)
+        self.err32 = {name: plane_err(self.ref32[name], self.ref64[name]) for name in self.ref64}
+
+    def _reference(self, dtype):
+        v, kind = self.v, self.v["kind"]
+        B, ci, co, H, W = v["shape"]
+        emulate = dtype == torch.float32
+        m = {"f2": 2, "small": 0, "s2": 0, "s2_fn": 0}.get(kind, 4)
+        out = {}
+        if kind in ("s2", "s2_fn"):
+            out["y"] = conv_s2(self.x, self.w, self.bias, v["pad"], dtype)
+        else:
+            x = self.x if kind != "gn" else gn_silu(self.x, self.off, self.gamma, self.beta, GN_GROUPS, GN_EPS, dtype)
+            if emulate and m:
+                out["y"] = winograd_emulate(x, self.w, self.bias, self.res, m=m)
+            else:
+                y = F.conv2d(x.to(dtype), self.w.to(dtype), None if self.bias is None else self.bias.to(dtype), padding=1)
+                out["y"] = y if self.res is None else y + self.res.to(dtype)
+        if v["bwd"]:
+            dy = self.dy if kind != "s2_fn" else zero_stuffed(self.dy, v["pad"], H, W)      # (the stride-2 gradient runs on the F(4x4) kernels)
+            wb = backward_filter(self.w)
+            out["dx"] = (winograd_emulate(dy, wb, m=m or 4) if emulate else F.conv2d(dy.double(), wb.double(), padding=1))
+        return out
+
+
+@functools.lru_cache(maxsize=8)
+def _case(name, family, seed):
+    return Case(BY_NAME[name], family, seed)
+
+
+def case(v, family, seed=11) -> Case:
+    return _case(v["name"], family, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# error metric
+# ---------------------------------------------------------------------------------------------------------------------
+def plane_maxima(y64):
+    return y64.abs().flatten(2).amax(-1)                          # [B, C]
+
+
+def plane_err(y, y64) -> float:
+    """max over (b, c) of max|y - y64| / max|y64| within that output plane."""
+    return ((y.double() - y64).abs().flatten(2).amax(-1) / plane_maxima(y64)).max().item()
+
+
+def whole_tensor_bound_accepts(y, y64) -> bool:
+    """The bound of the earlier convolution tests: assert_close(rtol 1e-4, atol 6e-5 * max|ref|) over the whole tensor."""
+    return bool(((y.double() - y64).abs() <= 6e-5 * y64.abs().max() + 1e-4 * y64.abs()).all())
+
+
+def input_conditions(c: Case):
+    """The conditions on a case's inputs: everything finite, no output identically zero, every fp64 plane maximum at least
+    MIN_PLANE of the global maximum.  -> name -> smallest plane maximum / global maximum."""
+    for t in (c.x, c.w, c.bias, c.res, c.dy):
+        assert t is None or (t.dtype == torch.float32 and bool(torch.isfinite(t).all()))
+    found = {}
+    for name, y64 in c.ref64.items():
+        assert bool(torch.isfinite(y64).all()) and bool(torch.isfinite(c.ref32[name]).all()), name
+        pm = plane_maxima(y64)
+        assert pm.max().item() > 0, f"{name} is identically zero"
+        found[name] = (pm.min() / pm.max()).item()
+        assert found[name] >= MIN_PLANE, f"{c.v['name']} {c.family} {name}: a plane's maximum is {found[name]:.2e} of the global maximum"
+    return found
+
+
+def assert_conv_close(got, c: Case, what="", m=None):
+    """Every output of `got` (name -> CPU tensor) is finite and within m x the fp32 reference's own per-plane error (+1e-7) of the
+    fp64 reference; m = M[kernel family of that output] unless given.  One line per output; -> name -> (err, err_fp32ref)."""
+    bad, report = [], {}
+    for name, x in got.items():
+        y64 = c.ref64[name]
+        assert tuple(x.shape) == tuple(y64.shape), f"{what} {name}: shape {tuple(x.shape)}"
+        mm = m if m is not None else M[c.v["mfam"][name]]
+        err, e32 = plane_err(x, y64), c.err32[name]
+        need = max(err - ABS_SLACK, 0.0) / e32 if e32 > 0 else (0.0 if err <= ABS_SLACK else math.inf)
+        report[name] = (err, e32)
+        print(f"conv-edge {what} {c.family} {name}: err {err:.3e} fp32ref {e32:.3e} ratio {err / e32 if e32 > 0 else math.inf:.2f} "
+              f"needs_m {need:.2f}")
+        finite = bool(torch.isfinite(x).all())
+        if not finite or not err <= mm * e32 + ABS_SLACK:
+            bad.append(f"{name}: {'NOT FINITE, ' if not finite else ''}err {err:.3e} > {mm} x {e32:.3e} + {ABS_SLACK:.0e}")
+    assert not bad, f"{what} [{c.family}, (B,Cin,Cout,H,W)={c.v['shape']}]: " + "; ".join(bad)
+    return report
+
+
+def block_statistics(y, pixels_y, pixels_x):
+    """fp64 {mean, M2 = sum (y - mean)^2} of y [B,C,H,W] over consecutive groups of 16 tiles of pixels_y x pixels_x (row-major
+    tiles within an image): what the F(4x4) epilogues leave behind, [B, C, blocks, 2]."""
+    B, C, H, W = y.shape
+    t = y.double().reshape(B, C, H // pixels_y, pixels_y, W // pixels_x, pixels_x).permute(0, 1, 2, 4, 3, 5)
+    t = t.reshape(B, C, -1, 16 * pixels_y * pixels_x)
+    mean = t.mean(-1)
+    return torch.stack([mean, ((t - mean[..., None]) ** 2).sum(-1)], dim=-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launch plans, restated from the sources (a change there must be repeated here, and in VARIANTS)
+# ---------------------------------------------------------------------------------------------------------------------
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def wino4_use_c128(cout, tiles):
+    """csrc/skp_conv_wino4.hip, wino4_use_c128 (routes.wino4_form names the same choice for the ledger)."""
+    return tiles >= 128 and (cout % 128 == 0 or (cout > 128 and cout % 128 >= 64))
+
+
+def wino4_grid(cout, tiles, S, raw=False):
+    """csrc/skp_conv_wino4.hip, wino4_grid (raw: wino4r_grid) -> dict(c128, ntb, ncg, tb_per_xcd, gx, rounds)."""
+    c128 = (not raw) and wino4_use_c128(cout, tiles)
+    ntb = _cdiv(tiles, 16) if c128 else _cdiv(tiles, 32)
+    ncg = cout // 64 if raw else (_cdiv(cout, 128) if c128 else _cdiv(cout, 64))
+    tbx = _cdiv(ntb, 8) if ntb >= (64 if c128 else 32) else 0
+    if tbx:
+        gx = 8 * tbx * ncg
+        rounds = _cdiv(gx * S, 256)
+    else:
+        upx = _cdiv(ncg * S, 8)
+        gx = 8 * upx * ntb
+        rounds = _cdiv(upx * ntb, 32)
+    return {"c128": c128, "ntb": ntb, "ncg": ncg, "tb_per_xcd": tbx, "gx": gx, "rounds": rounds}
+
+
+def _legal_split(nsteps, S):
+    return 1 <= S <= 16 and (S - 1) * _cdiv(nsteps, S) < nsteps
+
+
+def wino4_plan(B, Cin, Cout, H, W, forced=0, raw=False):
+    """csrc/skp_conv_wino4.hip, wino4_plan (raw: wino4r_plan): the number of K splits; `forced`: the wino_split override."""
+    tiles, nsteps = B * (H // 4) * (W // 4), Cin // 16
+    out_bytes = float(B * Cout * H * W * 4)
+    if forced and _legal_split(nsteps, forced):
+        return forced
+    if raw:
+        stage_us, over, gain = (2.7, 2.0, 0.97) if tiles <= 16 else (4.8, 2.5, 0.97)
+    else:
+        c128 = wino4_use_c128(Cout, tiles)
+        ragged = c128 and Cout % 128 != 0
+        stage_us, over, gain = ((4.8 if ragged else 3.9) if c128 else 5.6), 2.0, (0.95 if ragged else 0.92)
+    best, best_cost = 1, 1e30
+    for S in range(1, 17):
+        per = _cdiv(nsteps, S)
+        if (S - 1) * per >= nsteps:
+            continue
+        cost = wino4_grid(Cout, tiles, S, raw)["rounds"] * (per + over) * stage_us
+        if S > 1:
+            cost += 6.0 + (S + 1) * out_bytes / 8.0e6
+        if cost < best_cost * (gain if S > 1 else 1.0):
+            best, best_cost = S, cost
+    return best
+
+
+def wino4_facts(B, Cin, Cout, H, W, S, ncu=256, raw=False):
+    """What a launch of S K-splits does, from the restated grid and the id order of csrc/skp_wino4_common.h (w4_work)."""
+    tpi = (H // 4) * (W // 4)
+    tiles = B * tpi
+    g = wino4_grid(Cout, tiles, S, raw)
+    c128, ntb, ncg, tbx = g["c128"], g["ntb"], g["ncg"], g["tb_per_xcd"]
+    block, cgw = (16, 128) if c128 else (32, 64)
+    stages = Cin // 16
+    per = _cdiv(stages, S)
+    ids = g["gx"] * S if tbx else g["gx"]
+    launched = min(ids, ncu & ~7) if (c128 and ncu >= 8) else ids
+    images = max((min((t + 1) * block, tiles) - 1) // tpi - (t * block) // tpi + 1 for t in range(ntb))
+    return {"form": "raw" if raw else ("c128" if c128 else "c64"), "S": S, "stages": tuple([per] * (S - 1) + [stages - (S - 1) * per]),
+            "tiles": tiles, "ntb": ntb, "ncg": ncg, "order": "banded" if tbx else "unit", "tb_per_xcd": tbx, "ids": ids,
+            "launched": launched, "persistent": ids > launched,
+            "ragged_band": bool(tbx) and 8 * tbx > ntb, "empty_xcd": bool(tbx) and 7 * tbx >= ntb,
+            "idle_ids": (not tbx) and 8 * _cdiv(ncg * S, 8) > ncg * S, "units": ncg * S,
+            "ragged_cg": Cout % cgw != 0, "ragged_tb": tiles % block != 0, "images_in_a_block": images}
+
+
+def wino2_plan(B, Cin, Cout, H, W, variant):
+    """csrc/skp_conv_wino.hip, wino_plan / wino_pick_split -> (variant, K splits)"""
+    if variant == 0:
+        variant = 1 if Cin % 32 == 0 else 2
+    tiles = B * ((W + 1) // 2) * ((H + 1) // 2)
+    ntile, cg, kc, stage_us = (64, 64, 16, 3.4) if variant == 2 else (32, 128, 32, 6.8)
+    if Cin % kc:
+        return variant, 0
+    wgs = _cdiv(tiles, ntile) * _cdiv(Cout, cg)
+    if (H * W) % 4:
+        return variant, 1
+    nsteps, out_bytes = Cin // kc, float(B * Cout * H * W * 4)
+    best, best_cost = 1, 1e30
+    for S in range(1, 17):
+        if nsteps % S:
+            continue
+        cost = _cdiv(wgs * S, 256) * (nsteps // S + 1.0) * stage_us
+        if S > 1:
+            cost += 6.0 + (S + 1) * out_bytes / 4.0e6
+        if cost < best_cost * (0.92 if S > 1 else 1.0):
+            best, best_cost = S, cost
+    return variant, best
+
+
+def s2_splits(B, Cin, Cout, H, W):
+    """csrc/skp_conv_s2.hip, s2_splits (8 x 16 output pixels x 128 channels per workgroup)"""
+    wgs = B * ((H // 2) // 8) * ((W // 2) // 16) * _cdiv(Cout, 128)
+    if wgs >= 256:
+        return 1
+    s = min(_cdiv(512, wgs), (Cin >> 4) // 4, 8)
+    return 1 if s < 2 else s
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the variants: (entry point, shape, tune keys, what it must reach)
+# ---------------------------------------------------------------------------------------------------------------------
+def _v(name, kind, shape, reach, tune=None, split=True, bias=True, res=False, bwd=False, routed=None, variant=0, pad=1, off=False,
+       stats=False, ws=False):
+    B, ci, co, H, W = shape
+    mf = {"f4": "f4", "f4_stats": "f4", "gn": "gn", "f4r": "f4r", "f2": "f2", "s2": "s2", "s2_fn": "s2", "small": "small"}[kind]
+    if kind in ("s2", "s2_fn"):
+        tiles, seam, seam_out = B * (H // 16) * (W // 32), (16, 32), (8, 16)
+    elif kind == "f2":
+        tiles, seam, seam_out = B * ((H + 1) // 2) * ((W + 1) // 2), (2, 2), (2, 2)
+    else:
+        tiles, seam, seam_out = B * (H // 4) * (W // 4), (4, 4), (4, 4)
+    return {"name": name, "kind": kind, "shape": shape, "reach": reach, "tune": tune or {}, "split": split, "bias": bias, "res": res,
+            "bwd": bwd, "routed": routed, "variant": variant, "pad": pad, "off": off, "stats": stats, "ws": ws, "seam": seam,
+            "seam_out": seam_out, "mfam": {"y": mf, "dx": "f4" if kind == "s2_fn" else mf},
+            "families": BIG_FAMILIES if (kind != "small" and tiles > 1000) else FAMILIES}
+
+
+C128 = ("conv3x3", "wino4_c128")
+VARIANTS = [
+    # ---- F(4x4,3x3), transformed filter (ops._conv3x3_f4_raw); `reach` is a subset of wino4_facts at 256 CUs
+    _v("f4-c64-one-block", "f4", (2, 32, 32, 8, 8), {"form": "c64", "S": 1, "ntb": 1, "ncg": 1, "ragged_tb": True}, bwd=True),
+    _v("f4-c64-three-images-ragged-cg", "f4", (3, 16, 80, 12, 12),
+       {"form": "c64", "S": 1, "tiles": 27, "ntb": 1, "ncg": 2, "ragged_cg": True, "images_in_a_block": 3}, res=True, bwd=True),
+    _v("f4-c64-6-tiles-S3", "f4", (1, 48, 64, 8, 12), {"form": "c64", "S": 3, "tiles": 6, "stages": (1, 1, 1)}, bwd=True),
+    _v("f4-c64-6-tiles-unsplit", "f4", (1, 48, 64, 8, 12), {"form": "c64", "S": 3, "tiles": 6}, split=False, bwd=True),
+    _v("f4-c64-banded-ragged-band", "f4", (1, 16, 64, 132, 128),
+       {"form": "c64", "S": 1, "ntb": 33, "order": "banded", "tb_per_xcd": 5, "ragged_band": True, "empty_xcd": True}, bwd=True),
+    _v("f4-c128-one-group", "f4", (2, 32, 128, 32, 32), {"form": "c128", "S": 1, "ncg": 1, "ntb": 8, "order": "unit"}, res=True,
+       bwd=True, routed=C128),
+    _v("f4-c128-ragged-320", "f4", (2, 16, 320, 32, 32), {"form": "c128", "S": 1, "ncg": 3, "ragged_cg": True}, res=True, bwd=True),
+    _v("f4-c128-straddle-S5", "f4", (3, 80, 128, 20, 36),
+       {"form": "c128", "S": 5, "stages": (1, 1, 1, 1, 1), "ntb": 9, "ragged_tb": True, "images_in_a_block": 2}, bwd=True),
+    _v("f4-c128-straddle-unsplit", "f4", (3, 80, 128, 20, 36), {"form": "c128", "S": 5, "ntb": 9, "ragged_tb": True}, split=False, bwd=True),
+    _v("f4-c128-persistent-banded", "f4", (2, 16, 384, 128, 128),
+       {"form": "c128", "S": 1, "order": "banded", "ids": 384, "persistent": True, "ragged_band": False}, bwd=True),
+    _v("f4-c128-persistent-ragged-band", "f4", (1, 16, 256, 132, 256),
+       {"form": "c128", "S": 1, "order": "banded", "ids": 272, "ntb": 132, "tb_per_xcd": 17, "persistent": True, "ragged_band": True}, bwd=True),
+    _v("f4-c128-persistent-unit-idle-S12", "f4", (2, 192, 384, 32, 32),
+       {"form": "c128", "S": 12, "order": "unit", "ids": 320, "units": 36, "idle_ids": True, "persistent": True,
+        "stages": (1,) * 12}, tune={"wino_split": 12}, res=True, bwd=True, routed=C128),
+    _v("f4-c128-persistent-3-stages", "f4", (2, 48, 384, 128, 128),
+       {"form": "c128", "S": 1, "stages": (3,), "order": "banded", "ids": 384, "persistent": True}),
+    _v("f4-c128-persistent-uneven-S2", "f4", (2, 48, 384, 128, 128),
+       {"form": "c128", "S": 2, "stages": (2, 1), "order": "banded", "ids": 768, "persistent": True}, tune={"wino_split": 2}),
+    _v("f4-c128-unit-planned-S6", "f4", (2, 192, 384, 32, 32), {"form": "c128", "S": 6, "stages": (2,) * 6, "order": "unit", "ids": 192},
+       res=True, bwd=True),
+    _v("f4-c128-unit-unsplit", "f4", (2, 192, 384, 32, 32), {"form": "c128", "S": 6, "order": "unit"}, split=False, bwd=True),
+    _v("f4-c64-uneven-forced-S4", "f4", (2, 112, 64, 16, 16), {"form": "c64", "S": 4, "stages": (2, 2, 2, 1)},
+       tune={"wino_split": 4}, res=True, bwd=True),
+    _v("f4-c64-planned-S7", "f4", (2, 112, 64, 16, 16), {"form": "c64", "S": 7, "stages": (1,) * 7}, res=True, bwd=True),
+    _v("f4-c64-planned-S7-unsplit", "f4", (2, 112, 64, 16, 16), {"form": "c64", "S": 7}, split=False, bwd=True),
+    _v("f4-c128-one-per-cu", "f4", (1, 16, 128, 64, 128), {"form": "c128", "S": 1, "ids": 256, "launched": 256, "persistent": False}, bwd=True),
+    # ---- the statistics epilogue (skp_conv3x3_f4_stats_f32): y bit-equal to the plain launch, {mean, M2} of its own y
+    _v("f4-stats-c64", "f4_stats", (1, 32, 64, 64, 64), {"form": "c64", "S": 1}, stats=True),
+    _v("f4-stats-c128", "f4_stats", (1, 32, 128, 64, 64), {"form": "c128", "S": 1}, stats=True, res=True),
+    # ---- GroupNorm(+off)+SiLU folded into the patch load (ops.conv3x3_gn_silu -> skp_conv3x3_f4_gn_f32)
+    _v("gn-c128-smallest", "gn", (2, 32, 128, 32, 32), {"form": "c128", "S": 1, "ncg": 1}, routed=C128),
+    _v("gn-c128-off-stats", "gn", (2, 32, 128, 32, 32), {"form": "c128", "S": 1, "ncg": 1}, off=True, stats=True, res=True, routed=C128),
+    _v("gn-c128-ragged-320-off", "gn", (2, 32, 320, 32, 32), {"form": "c128", "S": 1, "ncg": 3, "ragged_cg": True}, off=True,
+       routed=C128),
+    # ---- F(4x4,3x3), raw filter (ops._conv3x3_f4r_raw); wino_raw_max_tiles makes skp_conv3x3_f4r_ok answer 1 for these sizes
+    _v("f4r-one-block-S1", "f4r", (1, 272, 192, 4, 4), {"form": "raw", "S": 1, "tiles": 1}, tune={"wino_split": 1, "wino_raw_max_tiles": 64}),
+    _v("f4r-one-block-S2", "f4r", (1, 272, 192, 4, 4), {"form": "raw", "S": 2, "stages": (9, 8)}, tune={"wino_split": 2, "wino_raw_max_tiles": 64}),
+    _v("f4r-one-block-S3", "f4r", (1, 272, 192, 4, 4), {"form": "raw", "S": 3, "stages": (6, 6, 5)}, tune={"wino_split": 3, "wino_raw_max_tiles": 64},
+       res=True),
+    _v("f4r-32-tiles-S1", "f4r", (2, 256, 64, 16, 16), {"form": "raw", "S": 1, "tiles": 32, "ragged_tb": False},
+       tune={"wino_split": 1, "wino_raw_max_tiles": 64}, res=True, bwd=True),
+    _v("f4r-32-tiles-S2", "f4r", (2, 256, 64, 16, 16), {"form": "raw", "S": 2, "stages": (8, 8)}, tune={"wino_split": 2, "wino_raw_max_tiles": 64},
+       bwd=True),
+    _v("f4r-32-tiles-S3", "f4r", (2, 256, 64, 16, 16), {"form": "raw", "S": 3, "stages": (6, 6, 4)}, tune={"wino_split": 3, "wino_raw_max_tiles": 64},
+       res=True, bwd=True),
+    _v("f4r-18-tiles-S1", "f4r", (3, 320, 128, 8, 12), {"form": "raw", "S": 1, "tiles": 18, "ragged_tb": True, "images_in_a_block": 3},
+       tune={"wino_split": 1, "wino_raw_max_tiles": 64}, bwd=True),
+    _v("f4r-18-tiles-S2", "f4r", (3, 320, 128, 8, 12), {"form": "raw", "S": 2, "stages": (10, 10)}, tune={"wino_split": 2, "wino_raw_max_tiles": 64},
+       res=True, bwd=True),
+    _v("f4r-18-tiles-S3", "f4r", (3, 320, 128, 8, 12), {"form": "raw", "S": 3, "stages": (7, 7, 6)}, tune={"wino_split": 3, "wino_raw_max_tiles": 64},
+       bwd=True),
+    _v("f4r-12-tiles-one-block", "f4r", (2, 320, 128, 8, 12), {"form": "raw", "S": 1, "tiles": 12, "images_in_a_block": 2},
+       tune={"wino_split": 1, "wino_raw_max_tiles": 64}, res=True, bwd=True),
+    # ---- F(2x2,3x3) (ops._conv3x3_raw, variant 1: 128 channels x 32 tiles, variant 2: 64 x 64); reach: (variant, K splits)
+    _v("f2-v1-odd-7x5", "f2", (1, 64, 96, 7, 5), {"variant": 1, "S": 1}, variant=1),
+    _v("f2-v2-odd-7x5", "f2", (1, 64, 96, 7, 5), {"variant": 2, "S": 1}, variant=2, bwd=True),
+    _v("f2-v1-odd-33x17", "f2", (1, 96, 64, 33, 17), {"variant": 1, "S": 1}, variant=1, bwd=True),
+    _v("f2-v2-odd-33x17", "f2", (1, 96, 64, 33, 17), {"variant": 2, "S": 1}, variant=2, res=True),
+    _v("f2-v1-ragged-160", "f2", (3, 32, 160, 6, 10), {"variant": 1, "S": 1, "ragged_cg": True}, variant=1, res=True),
+    _v("f2-v2-ragged-160", "f2", (3, 32, 160, 6, 10), {"variant": 2, "S": 1, "ragged_cg": True}, variant=2, bwd=True),
+    _v("f2-v1-workspace", "f2", (1, 128, 64, 8, 8), {"variant": 1, "S": 4}, variant=1, res=True, bwd=True),
+    _v("f2-v1-workspace-unsplit", "f2", (1, 128, 64, 8, 8), {"variant": 1, "S": 4}, variant=1, split=False),
+    _v("f2-v2-workspace", "f2", (1, 128, 64, 8, 8), {"variant": 2, "S": 8}, variant=2),
+    # ---- stride 2, direct (skp_conv3x3_s2_f32 / _ws_f32; ops.conv3x3_s2 -> ConvS2Fn for the input gradient); reach: K splits
+    _v("s2-pad0-small", "s2", (1, 16, 32, 16, 32), {"S": 1}, pad=0),
+    _v("s2-pad1-small", "s2", (1, 16, 32, 16, 32), {"S": 1}, pad=1, bias=False),
+    _v("s2-pad0-ragged-96", "s2", (2, 48, 96, 16, 32), {"S": 1, "ragged_cg": True}, pad=0, bias=False),
+    _v("s2-pad1-ragged-96", "s2", (2, 48, 96, 16, 32), {"S": 1, "ragged_cg": True}, pad=1),
+    _v("s2-pad1-workspace", "s2", (1, 128, 32, 16, 64), {"S": 2}, pad=1, ws=True),
+    _v("s2-pad0-workspace", "s2", (1, 128, 32, 16, 64), {"S": 2}, pad=0, ws=True),
+    _v("s2-fn-pad0", "s2_fn", (2, 32, 64, 16, 32), {"S": 1}, pad=0, bwd=True,
+       routed={("conv3x3_s2", "s2_direct"): 1, ("conv3x3_s2.bwd_data", "zero_stuffed"): 1, ("conv3x3.bwd_data", "wino4_c64"): 1}),
+    _v("s2-fn-pad1", "s2_fn", (2, 32, 64, 16, 32), {"S": 1}, pad=1, bwd=True,
+       routed={("conv3x3_s2", "s2_direct"): 1, ("conv3x3_s2.bwd_data", "zero_stuffed"): 1, ("conv3x3.bwd_data", "wino4_c64"): 1}),
+    # ---- <= 4 input channels (ops.conv3x3_small)
+    _v("small-1ch-9x2", "small", (3, 1, 5, 9, 2), {}, routed=("conv_in", "small")),
+    _v("small-4ch-8x8", "small", (1, 4, 32, 8, 8), {}, routed=("conv_in", "small"), bias=False),
+    _v("small-3ch-128", "small", (2, 3, 128, 16, 32), {}, routed=("conv_in", "small")),
+    _v("small-3ch-128-want-stats", "small", (2, 3, 128, 16, 32), {}, routed=("conv_in", "small"), stats=True),
+]
+BY_NAME = {v["name"]: v for v in VARIANTS}
+assert len(BY_NAME) == len(VARIANTS)
+
+
+def expected_ledger(v):
+    r = v["routed"]
+    if r is None:
+        return None
+    led = dict(r) if isinstance(r, dict) else {r: 1}
+    if v["kind"] == "gn":
+        led[("group_norm", "gn_fold")] = 1
+        led[("group_norm.stats", "own_pass")] = 1
+    return led
+
+
+def assert_plan(ops, v, ncu=256):
+    """The shape of variant `v` reaches what it is listed for, by the restated plan AND by the library's host queries (call it
+    with the variant's overrides set).  -> the facts."""
+    lib, kind = ops.N.lib(), v["kind"]
+    B, ci, co, H, W = v["shape"]
+    out_bytes = B * co * H * W * 4
+    forced = int(lib.skp_tune_get(b"wino_split"))
+    assert forced == v["tune"].get("wino_split", 0)
+    if kind in ("f4", "f4_stats", "gn"):
+        S = wino4_plan(B, ci, co, H, W, forced)
+        facts = wino4_facts(B, ci, co, H, W, S, ncu)
+        assert lib.skp_conv3x3_f4_workspace(B, ci, co, H, W) == (S * out_bytes if S > 1 else 0), "the library plans other K splits"
+        assert ops.routes.wino4_form(co, B, H, W) == "wino4_" + facts["form"]
+        blocks = (H // 4) * (W // 4) // 16 if (S == 1 and (H // 4) * (W // 4) % 32 == 0) else 0
+        assert lib.skp_conv3x3_f4_stats_blocks(B, ci, co, H, W) == blocks
+        gn_ok = int(S == 1 and facts["form"] == "c128" and co <= 512)
+        assert lib.skp_conv3x3_f4_gn_ok(B, ci, co, H, W) == gn_ok
+        assert blocks > 0 or not v["stats"], "no statistics epilogue for this shape"
+        if kind == "gn":
+            assert gn_ok == 1
+            if v["name"] == "gn-c128-smallest":                   # nothing smaller is served: fewer tiles or fewer channels leave the form
+                assert lib.skp_conv3x3_f4_gn_ok(1, ci, co, H, W) == 0 and lib.skp_conv3x3_f4_gn_ok(B, ci, 64, H, W) == 0
+                assert lib.skp_conv3x3_f4_gn_ok(B, ci, co, H - 4, W) == 0
+    elif kind == "f4r":
+        S = wino4_plan(B, ci, co, H, W, forced, raw=True)
+        facts = wino4_facts(B, ci, co, H, W, S, ncu, raw=True)
+        vpad = _cdiv(facts["tiles"], 32) * 32
+        assert lib.skp_conv3x3_f4r_workspace(B, ci, co, H, W) == 36 * ci * vpad * 4 + (S * out_bytes if S > 1 else 0)
+        assert lib.skp_conv3x3_f4r_ok(B, ci, co, H, W) == 1
+    elif kind == "f2":
+        variant, S = wino2_plan(B, ci, co, H, W, v["variant"])
+        facts = {"variant": variant, "S": S, "ragged_cg": co % (64 if variant == 2 else 128) != 0}
+        assert lib.skp_conv3x3_workspace(B, ci, co, H, W, v["variant"]) == (S * out_bytes if S > 1 else 0)
+    elif kind in ("s2", "s2_fn"):
+        S = s2_splits(B, ci, co, H, W)
+        facts = {"S": S, "ragged_cg": co % 128 != 0}
+        assert lib.skp_conv3x3_s2_workspace(B, ci, co, H, W) == (S * out_bytes // 4 if S > 1 else 0)
+        assert lib.skp_conv3x3_s2w_ok(B, ci, co, H, W, v["pad"]) == 0, "this shape belongs to the polyphase kernel"
+        assert (S > 1) == v["ws"]
+    else:
+        assert kind == "small" and ci <= 4 and W % 2 == 0
+        facts = {"stats_blocks": int(lib.skp_conv3x3_small_stats_blocks(B, ci, co, H, W))}
+    for key, want in v["reach"].items():
+        assert facts[key] == want, f"{v['name']}: {key} is {facts[key]}, listed as {want}"
+    return facts
