@@ -16,6 +16,7 @@
  *                                           (bicubic up-res softmax map, per-head store, layer/head mean)
  *   skp_cross_attn_fwd_f32 / _bwd_f32       ptp_utils.py:493-506,540 (ordinary softmax(QK^T)V, cross layers)
  *   skp_self_attn_fwd_f32 / _bwd_f32        ptp_utils.py:493-506,540 (self-attention layers, flash-style)
+ *   skp_text_attn_fwd_f32                   ptp_utils.py:436-439 (model.text_encoder: the causal attention of the CLIP towers)
  *   skp_flash_attn_fwd_f32 / _bwd_f32       ptp_utils.py:493-506,540 (any key count: cross layers with T > 128 tokens)
  *   skp_conv3x3[_f4]_f32 / skp_conv3x3_s2_f32 / skp_conv3x3_small_f32  3x3 convolutions of the frozen UNet / VAE blocks (ptp_utils.py:227-229, 289-304)
  *   skp_group_norm_fwd_f32 / _bwd_f32       GroupNorm+SiLU of the hooked UNet / VAE forward (ptp_utils.py:227-229, 289-304)
@@ -201,6 +202,17 @@ int skp_cross_attn_bwd_f32(const float* q, const float* k, const float* v, const
                            const float* dout, const float* lse, float* dq, float* dk, float* dv,
                            float* workspace, int B, int Bk, int H, int N, int T, int d, float scale,
                            void* stream);
+
+/* Causal self-attention forward of the CLIP text towers (the reference's model.text_encoder(input_ids)[0], ptp_utils.py:436-439),
+ * fp32 MFMA, K/V staged in LDS, masked softmax over the keys in registers (the mask goes onto the logits before the row maximum):
+ *   out[b,i,h*d+c] = sum_{j<=i} softmax_{j<=i}(scale * q[b,i,h,:].k[b,j,h,:]) * v[b,j,h*d+c]
+ * q, k, v: [B,N,.] read with a row stride of `ld` floats (ld >= H*d, ld % 4 == 0, bases 16-byte aligned): three column bands of one
+ * stacked [B*N, 3*H*d] projection output, or dense tensors with ld = H*d.  out: dense [B,N,H*d].  No log-sum-exp, no backward
+ * (the towers are frozen).  Limits: N <= 128, d in {32,64}; skp_text_attn_fwd_ok() == 1 says a shape is served.
+ * Errors: SKP_E_BADARG for a null or misaligned pointer or a non-positive size, SKP_E_RANGE for a shape outside the limits. */
+int skp_text_attn_fwd_ok(int B, int H, int N, int d, int ld);
+int skp_text_attn_fwd_f32(const float* q, const float* k, const float* v, float* out,
+                          int B, int H, int N, int d, int ld, float scale, void* stream);
 
 /* Token-group form of the backward.  mode 1: writes dot_io[b,l*H+h,p] = sum_{t in group} P*dM/(L*H) only;
  * mode 2: reads dot_io = that sum over ALL groups and writes this group's columns of dS[l]; mode 0 as above.

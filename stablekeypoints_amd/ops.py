@@ -658,6 +658,71 @@ def cross_attention(q, k, v, heads: int, scale: float):
 
 
 # ---------------------------------------------------------------------------------------------
+# causal self-attention of the CLIP text towers (csrc/skp_text_attn.hip)      ptp_utils.py:436-439
+# ---------------------------------------------------------------------------------------------
+# "auto": the causal kernel wherever it serves the shape (N <= 128, heads of 32 / 64 channels: all three product towers), library
+# GEMMs + a masked softmax elsewhere; "lib" (tests): the library everywhere.
+TEXT_ATTN_MODE = "auto"
+TEXT_ATTN_MODES = ("auto", "lib")
+
+
+def text_attn_supported(width: int, heads: int, n_tokens: int) -> bool:
+    return (width % heads == 0
+            and N.lib().skp_text_attn_fwd_ok(1, int(heads), int(n_tokens), int(width) // int(heads), int(width)) == 1)
+
+
+def _text_attn_lib(q, k, v, heads: int, scale: float):
+    """Library route of the same core: batched GEMMs and a softmax over the logits with -inf above the diagonal."""
+    B, Nn, C = q.shape
+    qh, kh, vh = (t.reshape(B, Nn, heads, C // heads).permute(0, 2, 1, 3) for t in (q, k, v))
+    S = torch.matmul(qh, kh.transpose(-1, -2)) * scale
+    S = S.masked_fill(torch.ones(Nn, Nn, device=q.device, dtype=torch.bool).triu(1), float("-inf"))
+    return torch.matmul(torch.softmax(S, dim=-1), vh).permute(0, 2, 1, 3).reshape(B, Nn, C)
+
+
+def text_attention(qkv_or_q, k, v, heads: int, scale: float):
+    """out[b,i] = merge_heads(softmax_{j<=i}(scale q_i k_j^T) v); no gradient.  Either q, k, v [B,N,C] each (dense, or views with one
+    common row stride such as the column bands of a stacked projection), or `qkv_or_q` [B,N,3C] holding q | k | v side by side and
+    k = v = None: the kernel reads the three bands in place.  -> dense [B,N,C].  Notes `text.attention`: `causal_fused`, or
+    `lib_core` for a head size or length the kernel does not serve and under TEXT_ATTN_MODE = "lib"."""
+    if TEXT_ATTN_MODE not in TEXT_ATTN_MODES:
+        raise ValueError(f"ops.TEXT_ATTN_MODE must be one of {TEXT_ATTN_MODES}, got {TEXT_ATTN_MODE!r}")
+    if (k is None) != (v is None):
+        raise RuntimeError("text_attention: pass q, k and v, or one packed q | k | v tensor with k = v = None")
+    if k is None:
+        qkv = _dev(qkv_or_q, "qkv")
+        if qkv.dim() != 3 or qkv.shape[-1] % 3:
+            raise RuntimeError(f"text_attention: packed q | k | v must be [B, N, 3C], got {tuple(qkv.shape)}")
+        C = qkv.shape[-1] // 3
+        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+    else:
+        q, k, v = qkv_or_q, k, v
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if not t.is_cuda or t.dtype != torch.float32:
+                _dev(t, name)                                    # raises: host tensor or another dtype
+        if q.dim() != 3 or k.shape != q.shape or v.shape != q.shape:
+            raise RuntimeError(f"text_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must be equal [B, N, C]")
+        strides = {t.stride() for t in (q, k, v)}
+        B_, N_, C_ = q.shape
+        ld = q.stride(1)
+        if not (len(strides) == 1 and q.stride(2) == 1 and ld >= C_ and ld % 4 == 0 and (B_ == 1 or q.stride(0) == N_ * ld)
+                and all(t.data_ptr() % 16 == 0 for t in (q, k, v))):
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    B, Nn, C = q.shape
+    if C % heads:
+        raise RuntimeError(f"text_attention: width {C} is no multiple of {heads} heads")
+    d, ld = C // heads, q.stride(1)
+    if TEXT_ATTN_MODE == "lib" or N.lib().skp_text_attn_fwd_ok(B, heads, Nn, d, ld) != 1 or any(t.data_ptr() % 16 for t in (q, k, v)):
+        routes.note("text.attention", "lib_core")
+        return _text_attn_lib(q, k, v, int(heads), float(scale))
+    routes.note("text.attention", "causal_fused")
+    out = torch.empty(B, Nn, C, device=q.device, dtype=torch.float32)
+    N.check(N.lib().skp_text_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, int(heads), Nn, d, ld,
+                                          float(scale), _stream()), "skp_text_attn_fwd_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # fused GroupNorm (+offset) (+SiLU) of the frozen network's blocks
 # ---------------------------------------------------------------------------------------------
 def group_norm_supported(x: torch.Tensor, groups: int) -> bool:

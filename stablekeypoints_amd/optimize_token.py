@@ -19,13 +19,17 @@ from .ldm.scheduler import DDIMScheduler
 
 
 def load_ldm(device, type="CompVis/stable-diffusion-v1-4", feature_upsample_res=256, my_token=None,
-             init_on_device=False, decoder=False, prediction_type=None):
+             init_on_device=False, decoder=False, prediction_type=None, text_encoder=False):
     """optimize_token.py:24-78.  `init_on_device` (extension, synthetic weights only): draw the seeded weights directly
     on `device` instead of on the host (multi-GPU start-up; see StableDiffusionPipeline.build).  `decoder` (extension): also
     build / load the VAE's decoder half, which only image sampling needs (ptp_utils.text2image_ldm_stable).  `prediction_type`
     (extension): what the UNet predicts, "epsilon" | "v_prediction" | "sample"; None reads it from
     `<checkpoint dir>/scheduler/scheduler_config.json` when `type` is a directory that has one (Stable Diffusion 2.1 at 768^2 is a
-    v-prediction model), else "epsilon" -- synthetic architectures included.  Only `scheduler.step` (image sampling) reads it."""
+    v-prediction model), else "epsilon" -- synthetic architectures included.  Only `scheduler.step` (image sampling) reads it.
+    `text_encoder` (extension): also build / load the CLIP text tower(s) and their tokenizer(s): `ldm.tokenizer` and
+    `ldm.text_encoder` (SDXL: also `ldm.tokenizer_2`, `ldm.text_encoder_2`), what `ptp_utils.encode_prompt` and the `uncond_prompt` of
+    `text2image_ldm_stable` need.  The default builds neither: `ldm.text_encoder` stays the raising stand-in and every other number
+    is the same with and without it."""
     if prediction_type is None:
         prediction_type = "epsilon"
         cfg = os.path.join(str(type), "scheduler", "scheduler_config.json")
@@ -37,7 +41,7 @@ def load_ldm(device, type="CompVis/stable-diffusion-v1-4", feature_upsample_res=
     scheduler.set_timesteps(50)                                   # NUM_DDIM_STEPS, optimize_token.py:33-34
     ldm = StableDiffusionPipeline.from_pretrained(type, use_auth_token=my_token, scheduler=scheduler,
                                                   init_device=device if init_on_device else None,
-                                                  with_decoder=decoder).to(device)
+                                                  with_decoder=decoder, with_text_encoder=text_encoder).to(device)
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -60,7 +64,9 @@ def load_ldm(device, type="CompVis/stable-diffusion-v1-4", feature_upsample_res=
         fuse_norms(ldm.vae)
         from . import tuning
         tuning.enable()                                 # measured GEMM algorithm choices for the frozen Linear layers
-    for module in (ldm.vae, ldm.text_encoder, ldm.unet):
+    for module in (ldm.vae, ldm.text_encoder, getattr(ldm, "text_encoder_2", None), ldm.unet):
+        if module is None:
+            continue
         for p in module.parameters():
             p.requires_grad = False
     return ldm, controllers, 1

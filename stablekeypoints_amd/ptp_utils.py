@@ -478,6 +478,35 @@ def latent_step(model, controller, latents, context, t, guidance_scale, low_reso
     return latents
 
 
+def _needs_text_encoder(model, what):
+    if getattr(model, "tokenizer", None) is None:
+        raise RuntimeError(f"{what}: this model was loaded without its text encoder; load it with "
+                           "optimize_token.load_ldm(..., text_encoder=True)")
+
+
+@torch.no_grad()
+def encode_prompt(model, prompts):
+    """ptp_utils.py:436-439: prompts (a string or a list of n strings) -> the context [n, 77, D] the UNet's cross-attention layers
+    take, on the model's device.
+      * SD-1.x / SD-2.x: `model.text_encoder(model.tokenizer(prompts, padding="max_length", max_length=77,
+        return_tensors="pt").input_ids)[0]`, the reference's call;
+      * SDXL: -> (context, pooled): the penultimate hidden states of the two towers side by side (768 + 1280 = 2048 channels) and the
+        second tower's pooled projection [n, 1280].  Feeding that pooled vector into sampling as `text_embeds` is OUT OF SCOPE:
+        `text2image_ldm_stable` keeps `default_added_cond`'s zeros, as it does for a learned embedding.
+    Padding is the tokenizer's pad id and there is no padding mask (how the Stable Diffusion pipelines call the towers).  The
+    model must have been loaded with `load_ldm(..., text_encoder=True)`."""
+    _needs_text_encoder(model, "encode_prompt")
+    prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+
+    def ids(tok):
+        return tok(prompts, padding="max_length", max_length=tok.model_max_length, return_tensors="pt").input_ids.to(model.device)
+    if getattr(model, "text_encoder_2", None) is None:
+        return model.text_encoder(ids(model.tokenizer))[0]
+    first = model.text_encoder(ids(model.tokenizer), penultimate=True)[0]
+    second, pooled = model.text_encoder_2(ids(model.tokenizer_2), penultimate=True)
+    return torch.cat([first, second], dim=-1), pooled
+
+
 @contextlib.contextmanager
 def _reproducible_library_convolutions():
     """Inside the block the library convolutions that the sampling path still reaches (few-tile layers, `conv3x3` / `lib`) may
@@ -499,7 +528,7 @@ def _reproducible_library_convolutions():
 def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                           generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
                           height: int = 512, width: int = 512, output_type: str = "uint8",
-                          uncond_embedding: Optional[torch.Tensor] = None):
+                          uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None):
     """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` deterministic DDIM
     steps and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
@@ -512,6 +541,9 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     `uncond_embedding` None (the default): like the reference's `low_resource=True` branch only the learned embedding conditions
     the UNet -- no unconditional pass, no text encoder, `guidance_scale` unused.  `uncond_embedding` [1, T', D] (keyword-only
     extension): classifier-free guidance of strength `guidance_scale` against it, `guided_latent_step`; T' may differ from T.
+    `uncond_prompt` (keyword-only extension, a string; "" is CLIP("")): the same with `encode_prompt(model, [uncond_prompt])` as the
+    unconditional embedding -- the reference's own unconditional input, and a negative prompt.  Not together with
+    `uncond_embedding`; the model must have been loaded with its text encoder (`load_ldm(..., text_encoder=True)`).
     What the UNet predicts (epsilon, v, sample) is the scheduler's `prediction_type` (`load_ldm(..., prediction_type=)`).
     The loop is not captured into a graph, eta is 0, DDIM is the only scheduler.  NOT reproduced: the reference's `torch.load` of two hard-coded files
     ("example_attn_maps_indices.pt", "outputs/indices.pt", whose contents it never uses) and
@@ -527,6 +559,15 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                            "optimize_token.load_ldm(..., decoder=True)")
     if height % 8 or width % 8:
         raise ValueError("height and width must be multiples of 8")
+    if uncond_prompt is not None:
+        if uncond_embedding is not None:
+            raise ValueError("text2image_ldm_stable: uncond_prompt and uncond_embedding are mutually exclusive")
+        if not isinstance(uncond_prompt, str):
+            raise ValueError("uncond_prompt must be one string")
+        _needs_text_encoder(model, "text2image_ldm_stable(uncond_prompt=...)")
+        uncond_embedding = encode_prompt(model, [uncond_prompt])
+        if isinstance(uncond_embedding, tuple):                    # SDXL: (context, pooled); the pooled vector is not fed to sampling
+            uncond_embedding = uncond_embedding[0]
     if isinstance(generator, (list, tuple)) or (latent is not None and latent.dim() == 4 and latent.shape[0] != 1):
         if isinstance(generator, (list, tuple)) and latent is not None and len(generator) != latent.shape[0]:
             raise ValueError(f"{len(generator)} generators for a latent of {latent.shape[0]} rows (a given latent is used as it is; "

@@ -59,6 +59,10 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "add_layer_norm": {"add_ln": "hip"},
     # VAE mid-block attention, one head of d = 512 (ops.vae_attn_route): the wide flash forward / library GEMMs + softmax
     "vae.attention": {"flash_wide": "hip", "lib_core": "library", "eager": "eager"},
+    # causal attention core of the CLIP text towers (ops.text_attention, ldm/clip.py): the short-sequence causal kernel (N <= 128,
+    # heads of 32 / 64 channels: every product tower) / library GEMMs + a masked softmax (another head size or length, and
+    # ops.TEXT_ATTN_MODE = "lib"; NOT a documented library route: no supported tower takes it) / the module tree on host tensors
+    "text.attention": {"causal_fused": "hip", "lib_core": "library", "host": "host"},
     "vae.tail": {"composed": "hip", "eager": "eager"},
     "vae.decoder": dict(_BLOCK),                          # Decoder.forward: fused tail (GroupNorm + SiLU, small-output conv_out) / its own
     # ptp_utils.latent2image: float NCHW image -> uint8 NHWC on the device (bytes cross to the host) / numpy on the host

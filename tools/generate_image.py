@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """Render what a learned embedding has learned: sample images from it (ptp_utils.text2image_ldm_stable) and write them out.
 
-    python tools/generate_image.py --model <checkpoint dir | synthetic-sd15 | tiny> --embedding emb.pt --out out/img
+    python tools/generate_image.py --model <checkpoint dir | synthetic-sd15 | tiny> (--embedding emb.pt | --prompt TEXT) --out out/img
                                    [--steps 50] [--seed 0] [--n 1] [--size 512] [--device cuda]
-                                   [--uncond unc.pt --guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
+                                   [--uncond unc.pt | --negative-prompt TEXT] [--guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
 
 `--embedding`: a tensor [1, T, D] (or [T, D]) saved with torch.save -- what `optimize_embedding` returns.  Image i is sampled from
 seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3]).
 `--uncond`: a tensor saved the same way, the unconditional / negative embedding of classifier-free guidance with strength
 `--guidance` (its token count may differ from the embedding's); without it only the embedding conditions the UNet.
+`--prompt TEXT`: sample from a plain prompt through the checkpoint's text encoder instead of a learned embedding;
+`--negative-prompt TEXT`: the unconditional side as a prompt (the empty string is valid and means CLIP("")).  Either one loads the
+text encoder and its tokenizer with the model (tools/encode_prompt.py writes the same embeddings to files).
 `--batch B`: B images per sampling call (the seeds, the images' starting noise and the file names do not depend on it).
 `--prediction-type`: what the UNet predicts; default: the checkpoint's scheduler/scheduler_config.json, else epsilon."""
 import argparse
@@ -22,7 +25,9 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", required=True)
-    ap.add_argument("--embedding", required=True)
+    ap.add_argument("--embedding", default=None)
+    ap.add_argument("--prompt", default=None)
+    ap.add_argument("--negative-prompt", default=None)
     ap.add_argument("--out", required=True)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
@@ -38,16 +43,26 @@ def main():
     import torch
     from stablekeypoints_amd import ptp_utils
     from stablekeypoints_amd.optimize_token import load_ldm
-    emb = torch.load(a.embedding, map_location="cpu", weights_only=True)
-    if emb.dim() == 2:
-        emb = emb[None]
+    if (a.embedding is None) == (a.prompt is None):
+        ap.error("exactly one of --embedding and --prompt")
+    if a.uncond is not None and a.negative_prompt is not None:
+        ap.error("--uncond and --negative-prompt are mutually exclusive")
+    emb = None
+    if a.embedding is not None:
+        emb = torch.load(a.embedding, map_location="cpu", weights_only=True)
+        if emb.dim() == 2:
+            emb = emb[None]
     unc = None
     if a.uncond is not None:
         unc = torch.load(a.uncond, map_location="cpu", weights_only=True)
         unc = unc[None] if unc.dim() == 2 else unc
     if a.batch < 1:
         ap.error("--batch must be at least 1")
-    ldm, controllers, _ = load_ldm(a.device, a.model, decoder=True, prediction_type=a.prediction_type)
+    ldm, controllers, _ = load_ldm(a.device, a.model, decoder=True, prediction_type=a.prediction_type,
+                                   text_encoder=a.prompt is not None or a.negative_prompt is not None)
+    if emb is None:
+        emb = ptp_utils.encode_prompt(ldm, [a.prompt])
+        emb = emb[0] if isinstance(emb, tuple) else emb
     controller = next(iter(controllers.values()))
     try:
         from PIL import Image
@@ -59,7 +74,7 @@ def main():
         gens = [torch.Generator().manual_seed(a.seed + i) for i in ids]
         image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps, guidance_scale=a.guidance,
                                                    generator=gens[0] if a.batch == 1 else gens, height=a.size, width=a.size,
-                                                   uncond_embedding=unc)
+                                                   uncond_embedding=unc, uncond_prompt=a.negative_prompt)
         for row, i in enumerate(ids):
             path = f"{a.out}_{i}" + (".png" if Image is not None else ".npy")
             if Image is not None:
