@@ -28,6 +28,7 @@
  *   skp_conv3x3_up2_f32 / skp_conv3x3_small_out_f32   Upsample2D and conv_out of image sampling (ptp_utils.py:316-322)
  *   skp_axpby_f32 / skp_ddim_step_f32       the scheduler step of ptp_utils.py:337-349 (plain / guided, epsilon, v or sample
  *                                           prediction, optional clamp, optional second copy of the result)
+ *   skp_sampler_step_f32                    the same step for the samplers the reference does not have (eta > 0, DPM-Solver++ 2M)
  *   skp_image_u8_nhwc_f32                   ptp_utils.py:320-322 (float NCHW image -> uint8 NHWC)
  */
 #ifndef SKP_H
@@ -462,6 +463,26 @@ int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, flo
  * SKP_E_BADARG: x / m_c / y NULL, n <= 0, copies outside {1, 2}, prediction outside {0, 1, 2}. */
 int skp_ddim_step_f32(const float* x, const float* m_c, const float* m_u, float* y, int64_t n, int copies, float guidance,
                       int prediction, float sa, float sb, float pa, float pb, int clip, void* stream);
+
+/* One step of the samplers of ldm/samplers.py (stochastic DDIM, DPM-Solver++(2M), SDE-DPM-Solver++(2M)) in one pass
+ * (skp_sampler_step.hip; ptp_utils.py `sampler_latent_step`).  Per element i < n:
+ *   m         = m_u ? m_u + guidance * (m_c - m_u) : m_c                 (classifier-free guidance; m_u may be NULL)
+ *   (x0, eps) = prediction 0 (epsilon): ((x - sb m) / sa, m)
+ *               prediction 1 (v):       (sa x - sb m, sa m + sb x)
+ *               prediction 2 (sample):  (m, (x - sa m) / sb)
+ *   x0        = clamp(x0, -1, 1) if clip        (eps stays as derived before the clamp)
+ *   y         = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise
+ *   x0_out    = x0                              (after the clamp: the next step's x0_prev)
+ * sa, sb = sqrt(a_t), sqrt(1 - a_t); cx, c0, ce, c1, cn: the sampler's row for this step; all computed by the host in fp64 and rounded
+ * once.  x0_prev may be NULL when c1 == 0 and noise when cn == 0; with a zero coefficient the buffer is not read, whatever it
+ * holds.  x0_out may be NULL (not written), else n floats.  y holds copies * n floats as for skp_ddim_step_f32.  y may alias x (with
+ * copies == 2, x may be the first copy) and x0_out may alias x0_prev; no other overlap.  16-byte accesses when every pointer given
+ * is 16-byte aligned (the second copy too when n % 4 == 0), scalar accesses otherwise; any n.  No atomics: bit-identical from call
+ * to call.  SKP_E_BADARG: x / m_c / y NULL, n <= 0, copies outside {1, 2}, prediction outside {0, 1, 2}, c1 != 0 with x0_prev NULL,
+ * cn != 0 with noise NULL. */
+int skp_sampler_step_f32(const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise, float* y,
+                         float* x0_out, int64_t n, int copies, float guidance, int prediction, float sa, float sb, float cx,
+                         float c0, float ce, float c1, float cn, int clip, void* stream);
 
 /* Image to bytes (ptp_utils.py `latent2image`): x float [B,3,H,W] in [0, 1] (the decoder's image epilogue) -> y uint8 [B,H,W,3],
  * y = (unsigned char)(x * 255.0f), truncating, no clamp: exactly what the host expression (x.permute(0,2,3,1) * 255).astype(uint8)

@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: libskp_hip.so has 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKP_LIB_PATH: another BUILD of the same library (same-box A/B of two kernel versions, tools/ab_build.py); never a fallback
 LIB_PATH = os.environ.get("SKP_LIB_PATH") or os.path.join(_HERE, "csrc", "libskp_hip.so")
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
@@ -102,6 +102,7 @@ SIGNATURES = {
     "skp_conv3x3_small_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "skp_axpby_f32": [_vp, _vp, _vp, _i64, _f, _f, _vp],
     "skp_ddim_step_f32": [_vp, _vp, _vp, _vp, _i64, _i, _f, _i, _f, _f, _f, _f, _i, _vp],
+    "skp_sampler_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _i, _vp],
     "skp_image_u8_nhwc_f32": [_vp, _vp, _i, _i, _i, _vp],
     "skp_conv3x3_f4_stats_blocks": [_i, _i, _i, _i, _i],
     "skp_conv3x3_f4_stats_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

@@ -1,0 +1,103 @@
+"""Sampler plans of the image-sampling loop (`ptp_utils.text2image_ldm_stable(..., sampler=)`): stochastic DDIM (eta in [0, 1]),
+DPM-Solver++(2M) and SDE-DPM-Solver++(2M), each as ONE linear update per step in the variance-preserving state the UNet sees.
+With a = alphas_cumprod, alpha = sqrt(a), sigma = sqrt(1 - a), primes at the step's target, lambda = log(alpha / sigma),
+h = lambda' - lambda and r = h_prev / h:
+
+    m        = m_u + g (m_c - m_u)   or   m_c
+    (x0,eps) from (x, m) by the prediction type with (sa, sb) = (alpha_t, sigma_t)        the three cases of DDIMScheduler.step
+    x0c      = clamp(x0, -1, 1) if clip_sample else x0                                    (eps stays as derived before the clamp)
+    y        = cx x + c0 x0c + ce eps + c1 x0_prev + cn noise,        x0_prev = the previous step's x0c
+
+    "ddim"         s = eta sqrt((1 - a') / (1 - a)) sqrt(1 - a / a');   c0 = alpha', ce = sqrt(1 - a' - s^2), cn = s, cx = c1 = 0
+    "dpm++2m"      cx = sigma' / sigma, cD = -alpha' expm1(-h);  y = cx x + cD D
+    "dpm++2m-sde"  cx = (sigma' / sigma) exp(-h), cD = alpha' (1 - exp(-2h)), cn = sigma' sqrt(1 - exp(-2h));  y = cx x + cD D + cn noise
+      D = x0c on the first step, on the last step (lower_order_final) and whenever sigma' == 0 -- there h is infinite and the
+          limit is written out: cx = cn = 0, cD = alpha';
+      D = (1 + 1 / (2r)) x0c - (1 / (2r)) x0_prev on every other step, so c0 = cD (1 + 1 / (2r)), c1 = -cD / (2r).
+
+A plan is host arithmetic in fp64 on the CPU-side schedule, as `DDIMScheduler._coefficients` is: nothing is read back from a device.
+It reads the model's scheduler and never writes to it -- `model.scheduler` stays what the optimisation path reads.  All samplers
+walk the "leading" timestep table of `DDIMScheduler.set_timesteps`.  Not built: Karras sigma spacing / fractional timesteps,
+Heun, UniPC, thresholding."""
+from __future__ import annotations
+
+import math
+from typing import List, NamedTuple, Tuple
+
+import torch
+
+SAMPLERS = ("ddim", "dpm++2m", "dpm++2m-sde")
+
+
+class StepCoef(NamedTuple):
+    """One step's host numbers, in the order `ops.sampler_step(coef=)` and skp_sampler_step_f32 take them."""
+    sa: float
+    sb: float
+    cx: float
+    c0: float
+    ce: float
+    c1: float
+    cn: float
+
+
+def is_stochastic(kind: str, eta: float = 0.0) -> bool:
+    return kind == "dpm++2m-sde" or (kind == "ddim" and eta > 0)
+
+
+class SamplerPlan:
+    """`SamplerPlan(scheduler, kind, eta).plan(n)` -> (timesteps, [StepCoef] * n).  `order=1` forces the first-order update on
+    every step of the two multistep solvers (what they do on their first and last step anyway)."""
+
+    def __init__(self, scheduler, kind: str = "ddim", eta: float = 0.0, order: int = 2):
+        if kind not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}, got {kind!r}")
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:                                # (NaN fails too)
+            raise ValueError(f"eta must be in [0, 1], got {eta!r}")
+        if eta != 0 and kind != "ddim":
+            raise ValueError(f"eta = {eta!r} belongs to sampler \"ddim\"; {kind!r} has no such parameter")
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order!r}")
+        self.kind, self.eta, self.order = kind, eta, order
+        self.alphas_cumprod = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)       # a copy: the scheduler is not touched
+        self.final_alpha_cumprod = float(scheduler.final_alpha_cumprod)
+        self.num_train_timesteps = int(scheduler.num_train_timesteps)
+        self.prediction_type = scheduler.prediction_type
+        self.clip_sample = bool(scheduler.clip_sample)
+
+    @property
+    def stochastic(self) -> bool:
+        return is_stochastic(self.kind, self.eta)
+
+    def plan(self, num_inference_steps: int) -> Tuple[torch.Tensor, List[StepCoef]]:
+        n = int(num_inference_steps)
+        if n < 1:
+            raise ValueError(f"num_inference_steps must be at least 1, got {num_inference_steps!r}")
+        stride = self.num_train_timesteps // n
+        timesteps = (torch.arange(0, n) * stride).flip(0)        # DDIMScheduler.set_timesteps' table
+        rows, h_prev = [], None
+        for i, t in enumerate(timesteps.tolist()):
+            a = float(self.alphas_cumprod[t])
+            a_p = float(self.alphas_cumprod[t - stride]) if t - stride >= 0 else self.final_alpha_cumprod
+            al, sg, al_p, sg_p = math.sqrt(a), math.sqrt(1.0 - a), math.sqrt(a_p), math.sqrt(1.0 - a_p)
+            if self.kind == "ddim":
+                s = self.eta * math.sqrt((1.0 - a_p) / (1.0 - a)) * math.sqrt(1.0 - a / a_p)
+                rows.append(StepCoef(al, sg, 0.0, al_p, math.sqrt(max(1.0 - a_p - s * s, 0.0)), 0.0, s))
+                continue
+            if sg_p == 0.0:                                      # h is infinite: the limit of either solver
+                rows.append(StepCoef(al, sg, 0.0, al_p, 0.0, 0.0, 0.0))
+                h_prev = None
+                continue
+            h = math.log(al_p / sg_p) - math.log(al / sg)
+            if self.kind == "dpm++2m":
+                cx, cd, cn = sg_p / sg, -al_p * math.expm1(-h), 0.0
+            else:
+                cx, cd, cn = sg_p / sg * math.exp(-h), -al_p * math.expm1(-2.0 * h), sg_p * math.sqrt(-math.expm1(-2.0 * h))
+            if self.order == 1 or i == 0 or i == n - 1 or h_prev is None:
+                c0, c1 = cd, 0.0
+            else:
+                r = h_prev / h
+                c0, c1 = cd * (1.0 + 0.5 / r), -cd * 0.5 / r
+            rows.append(StepCoef(al, sg, cx, c0, 0.0, c1, cn))
+            h_prev = h
+        return timesteps, rows

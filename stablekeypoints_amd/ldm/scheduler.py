@@ -1,7 +1,9 @@
 """Minimal DDIMScheduler with the behaviour the hot path consumes [3P diffusers==0.8.0]:
 `timesteps[i]`, `add_noise(latent, noise, t)`  (optimize_token.py:25-34, ptp_utils.py:221-223), and for image sampling
 `set_timesteps(n)` + `step(model_output, t, sample)` (ptp_utils.py:337-349): eta = 0; epsilon, v or sample prediction; optional
-classifier-free guidance mixed into the step.  Not built: eta > 0 (no variance noise), other schedulers, thresholding."""
+classifier-free guidance mixed into the step.  eta > 0, DPM-Solver++(2M) and its SDE form are plans of their own over this
+scheduler's schedule and timestep table (ldm/samplers.py; `text2image_ldm_stable(..., sampler=)`); this class and its `step` are
+what they always were.  Not built: thresholding."""
 from __future__ import annotations
 
 import torch

@@ -1523,6 +1523,41 @@ def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, g
     return out
 
 
+def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: float = 1.0, prediction="epsilon",
+                 clip: bool = False, copies: int = 1, out=None, x0_out=None):
+    """One step of a sampler of ldm/samplers.py in one pass (csrc/skp_sampler_step.hip, formula in include/skp.h): the guidance mix,
+    (x0, eps) by `prediction` and the clamp as in `ddim_step`, then y = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise with
+    `coef` = (sa, sb, cx, c0, ce, c1, cn) (a `samplers.StepCoef`).  -> y shaped like x, or with `copies=2` like torch.cat([x, x]).
+    `x0_prev` / `noise`: shaped like x; each may be None when its coefficient is 0.  `out`: as in `ddim_step` (it may be x, or
+    a doubled buffer whose first half x is).  `x0_out`: a contiguous float32 tensor shaped like x that receives the clamped x0; it
+    may be `x0_prev` itself (the history updated in place)."""
+    x, m_c = _dev(x, "x"), _dev(m_c, "m_c")
+    m_u = _dev(m_u, "m_u") if m_u is not None else None
+    noise = _dev(noise, "noise") if noise is not None else None
+    if x0_prev is not None and not (x0_prev.is_cuda and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous()):
+        raise RuntimeError("sampler_step: `x0_prev` must be a contiguous float32 device tensor")
+    if any(t is not None and t.shape != x.shape for t in (m_c, m_u, x0_prev, noise)):
+        raise RuntimeError("sampler_step: shapes differ")
+    pred = DDIM_PREDICTION.get(prediction, prediction)
+    if pred not in (0, 1, 2) or copies not in (1, 2):
+        raise ValueError(f"sampler_step: prediction {prediction!r} / copies {copies!r}")
+    sa, sb, cx, c0, ce, c1, cn = (float(v) for v in coef)
+    if (c1 != 0.0 and x0_prev is None) or (cn != 0.0 and noise is None):
+        raise ValueError("sampler_step: a nonzero c1 needs `x0_prev`, a nonzero cn needs `noise`")
+    n = x.numel()
+    if out is None:
+        out = torch.empty((copies * x.shape[0],) + tuple(x.shape[1:]) if x.dim() else (copies,), device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == copies * n):
+        raise RuntimeError("sampler_step: `out` must be a contiguous float32 device tensor of copies * x.numel() elements")
+    if x0_out is not None and not (x0_out.is_cuda and x0_out.dtype == torch.float32 and x0_out.is_contiguous()
+                                   and x0_out.numel() == n):
+        raise RuntimeError("sampler_step: `x0_out` must be a contiguous float32 device tensor of x.numel() elements")
+    N.check(N.lib().skp_sampler_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), _ptr(x0_prev), _ptr(noise), out.data_ptr(),
+                                         _ptr(x0_out), n, int(copies), float(guidance), int(pred), sa, sb, cx, c0, ce, c1, cn,
+                                         int(bool(clip)), _stream()), "skp_sampler_step_f32")
+    return out
+
+
 def image_u8_nhwc(x):
     """float [B,3,H,W] in [0, 1] -> uint8 [B,H,W,3] = (x.permute(0, 2, 3, 1) * 255) truncated, on the device
     (csrc/skp_ddim_step.hip; `ptp_utils.latent2image`)."""

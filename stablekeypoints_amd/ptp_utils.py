@@ -4,7 +4,8 @@ Kept names/signatures: `AttentionControl`, `AttentionStore`,
 `register_attention_control`, `find_pred_noise`, `run_and_find_attn`, `image2latent`,
 `find_top_k_gaussian`, `furthest_point_sampling`, `init_random_noise`, and the image-sampling entries `diffusion_step`,
 `latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461); `init_latents` and
-`guided_latent_step` are this port's batched / classifier-free-guidance companions of the last two.
+`guided_latent_step` are this port's batched / classifier-free-guidance companions of the last two, `sampler_latent_step` the step
+of the named samplers (ldm/samplers.py).
 
 What changes under the hood
   * the hooked cross-attention does NOT up-sample the layer input, re-project it and materialise a
@@ -478,6 +479,77 @@ def latent_step(model, controller, latents, context, t, guidance_scale, low_reso
     return latents
 
 
+def sampler_latent_step(model, controller, latents, context, t, guidance_scale, *, plan, coef, x0_hist, noise=None, doubled=False):
+    """One step of a sampler of ldm/samplers.py: the UNet forward(s) of `latent_step` (`context[0]` None: the conditional prediction
+    alone) or of `guided_latent_step` (one forward of 2n rows for contexts of equal length, two forwards otherwise; `doubled` as
+    there), then the sampler's linear update with the host numbers `coef` (a `samplers.StepCoef` of `plan`, whose prediction type
+    and clipping apply) and `controller.step_callback`.  `x0_hist` [n, C, h, w]: the previous step's clamped x0, read when
+    `coef.c1 != 0` and overwritten in place with this step's (the multistep solvers only; None for "ddim").  `noise` [n, C, h, w]:
+    this step's gaussian, read when `coef.cn != 0`.  float32 device tensors take one kernel, `ops.sampler_step`, that also
+    writes the second copy of a doubled result; host tensors and other dtypes evaluate the same formula in torch, in the input
+    dtype."""
+    uncond, cond = context
+    guided = uncond is not None
+    if doubled and not (guided and uncond.shape[1] == cond.shape[1]):
+        raise ValueError("sampler_latent_step: doubled latents need guidance with contexts of equal length")
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    pred_u = None
+    if guided and uncond.shape[1] == cond.shape[1]:
+        rows = latents if doubled else torch.cat([latents, latents])
+        ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
+        pred = _unet_forward_shared_context(model, rows, t, ctx)
+        pred_u, pred_c = pred[:n], pred[n:]
+        latents = rows[:n]
+    elif guided:
+        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
+        pred_c = _unet_forward_shared_context(model, latents, t, cond)
+    else:
+        pred_c = _unet_forward_shared_context(model, latents, t, cond)
+    prev = x0_hist if coef.c1 != 0 else None
+    nz = noise if coef.cn != 0 else None
+    if latents.is_cuda and all(v is None or v.dtype == torch.float32 for v in (latents, pred_c, pred_u, prev, nz, x0_hist)):
+        routes.note("sample.step", "sampler_step")
+        out = ops.sampler_step(latents, pred_c, pred_u, x0_prev=prev, noise=nz, coef=coef, guidance=float(guidance_scale),
+                               prediction=plan.prediction_type, clip=plan.clip_sample, copies=2 if doubled else 1, x0_out=x0_hist)
+    else:
+        routes.note("sample.step", "host")
+        m = pred_u + guidance_scale * (pred_c - pred_u) if guided else pred_c
+        if plan.prediction_type == "epsilon":
+            x0, eps = (latents - coef.sb * m) / coef.sa, m
+        elif plan.prediction_type == "v_prediction":
+            x0, eps = coef.sa * latents - coef.sb * m, coef.sa * m + coef.sb * latents
+        else:
+            x0, eps = m, (latents - coef.sa * m) / coef.sb
+        if plan.clip_sample:
+            x0 = x0.clamp(-1, 1)
+        out = coef.cx * latents + coef.c0 * x0 + coef.ce * eps
+        if prev is not None:
+            out = out + coef.c1 * prev
+        if nz is not None:
+            out = out + coef.cn * nz
+        if x0_hist is not None:
+            x0_hist.copy_(x0)
+        out = torch.cat([out, out]) if doubled else out
+    if controller is not None:
+        first = out[:n] if doubled else out
+        called = controller.step_callback(first)
+        if called is not first:
+            out = torch.cat([called, called]) if doubled else called
+    return out
+
+
+def _step_noise(plan, steps, latent, generator):
+    """The gaussians of a stochastic sampler, [steps, n, C, h, w] on the CPU: image i's row of step s is the s-th
+    torch.randn((1, C, h, w), generator=generators[i]) after that image's initial latent -- the rule of `init_latents`, so image i
+    of a batch sees the noise of the single-image call with its generator."""
+    gens = list(generator) if isinstance(generator, (list, tuple)) else [generator]
+    if any(g is None for g in gens) or len(gens) != latent.shape[0]:
+        raise ValueError(f"sampler {plan.kind!r}" + (f" with eta = {plan.eta}" if plan.kind == "ddim" else "") + " draws noise at "
+                         "every step: it needs a generator (one per image), also when `latent` is given")
+    shape = (1,) + tuple(latent.shape[1:])
+    return torch.stack([torch.cat([torch.randn(shape, generator=g) for g in gens]) for _ in range(steps)])
+
+
 def _needs_text_encoder(model, what):
     if getattr(model, "tokenizer", None) is None:
         raise RuntimeError(f"{what}: this model was loaded without its text encoder; load it with "
@@ -528,9 +600,10 @@ def _reproducible_library_convolutions():
 def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                           generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
                           height: int = 512, width: int = 512, output_type: str = "uint8",
-                          uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None):
-    """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` deterministic DDIM
-    steps and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
+                          uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None,
+                          sampler: Optional[str] = None, eta: float = 0.0):
+    """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` steps of `sampler`
+    (deterministic DDIM by default) and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
     noise [1, C, height/8, width/8] on the CPU (given, or drawn from `generator` on the CPU as the reference draws it).
 
@@ -545,7 +618,17 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     unconditional embedding -- the reference's own unconditional input, and a negative prompt.  Not together with
     `uncond_embedding`; the model must have been loaded with its text encoder (`load_ldm(..., text_encoder=True)`).
     What the UNet predicts (epsilon, v, sample) is the scheduler's `prediction_type` (`load_ldm(..., prediction_type=)`).
-    The loop is not captured into a graph, eta is 0, DDIM is the only scheduler.  NOT reproduced: the reference's `torch.load` of two hard-coded files
+    `sampler` (keyword-only extension; ldm/samplers.py): None -- the deterministic DDIM step of `model.scheduler`, the call as it
+    always was; "ddim" with `eta` in [0, 1] (eta = 0 is routed to that same step: the same bits as None); "dpm++2m"
+    (DPM-Solver++ 2M, second-order multistep: the usual choice at about 20 steps); "dpm++2m-sde".  All walk the timestep table
+    of `set_timesteps`; `eta` belongs to "ddim": a nonzero `eta` without a sampler or with another one raises ValueError.  A named sampler runs the same loop -- guided, doubled, batched or not
+    -- on one fused kernel per step (`sampler_latent_step`, ledger site `sample.step`), its fp64 host coefficients taken from a
+    plan that reads `model.scheduler` and leaves it as it is; the multistep solvers keep the previous step's x0 in one
+    [n, C, h, w] buffer, updated in place.  The stochastic ones ("ddim" with eta > 0, "dpm++2m-sde") draw their noise on the CPU
+    before the loop, image i's from `generator[i]` after its initial latent, one torch.randn((1, C, h, w)) per step -- image i
+    of a batch sees the noise of the single-image call with that generator -- and upload it once as [steps, n, C, h, w]; they
+    need a generator also when `latent` is given (ValueError otherwise).
+    The loop is not captured into a graph.  NOT reproduced: the reference's `torch.load` of two hard-coded files
     ("example_attn_maps_indices.pt", "outputs/indices.pt", whose contents it never uses) and
     `register_attention_control_generation`, which re-installs the attention math the module tree already computes.  `height`,
     `width` and `output_type` are keyword-only extensions (the reference fixes 512 x 512).  The scheduler's timestep table is
@@ -559,6 +642,17 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                            "optimize_token.load_ldm(..., decoder=True)")
     if height % 8 or width % 8:
         raise ValueError("height and width must be multiples of 8")
+    plan = None
+    if sampler is None and eta != 0:
+        raise ValueError(f"eta = {eta!r} needs sampler=\"ddim\": without a sampler the call is the deterministic DDIM step")
+    if sampler is not None:
+        from .ldm.samplers import SamplerPlan
+        plan = SamplerPlan(model.scheduler, sampler, eta)          # an unknown name or eta outside [0, 1]: ValueError
+        if plan.kind == "ddim" and plan.eta == 0:
+            plan = None                                            # the step the call always had
+    if plan is not None and plan.stochastic and generator is None:
+        raise ValueError(f"sampler {sampler!r}" + (f" with eta = {eta}" if sampler == "ddim" else "") + " draws noise at every "
+                         "step: it needs a generator (one per image), also when `latent` is given")
     if uncond_prompt is not None:
         if uncond_embedding is not None:
             raise ValueError("text2image_ldm_stable: uncond_prompt and uncond_embedding are mutually exclusive")
@@ -591,12 +685,22 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
         latents = torch.cat([latents, latents])
     sched = model.scheduler
     kept = (sched.timesteps, sched.num_inference_steps)
+    if plan is not None:
+        timesteps, coefs = plan.plan(num_inference_steps)
+        first = latents[:n]
+        x0_hist = None if plan.kind == "ddim" else torch.empty_like(first)
+        noise = _step_noise(plan, len(coefs), first, generator).to(first) if plan.stochastic else None     # one upload
     with _reproducible_library_convolutions():                 # the loop and the decode: one call, one result, bit for bit
-        sched.set_timesteps(num_inference_steps)
         try:
+            if plan is None:
+                sched.set_timesteps(num_inference_steps)         # (a plan has its own table and leaves the scheduler alone)
             with ops.up2_in_unet(latents.is_cuda):
-                for t in sched.timesteps:
-                    if guided:
+                for i, t in enumerate(sched.timesteps if plan is None else timesteps):
+                    if plan is not None:
+                        latents = sampler_latent_step(model, controller, latents, context, t, guidance_scale, plan=plan,
+                                                      coef=coefs[i], x0_hist=x0_hist, noise=None if noise is None else noise[i],
+                                                      doubled=doubled)
+                    elif guided:
                         latents = guided_latent_step(model, controller, latents, context, t, guidance_scale, doubled=doubled)
                     else:
                         latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)

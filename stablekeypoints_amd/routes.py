@@ -67,6 +67,9 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "vae.decoder": dict(_BLOCK),                          # Decoder.forward: fused tail (GroupNorm + SiLU, small-output conv_out) / its own
     # ptp_utils.latent2image: float NCHW image -> uint8 NHWC on the device (bytes cross to the host) / numpy on the host
     "image.u8": {"nhwc_u8": "hip", "host": "host"},
+    # the step of a named sampler (ptp_utils.sampler_latent_step; text2image_ldm_stable(sampler=) other than the eta = 0 DDIM
+    # step it always had, which has no gate and notes nothing): the fused step kernel / the formula in torch on host tensors
+    "sample.step": {"sampler_step": "hip", "host": "host"},
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),

@@ -3,6 +3,7 @@
 classifier-free guidance, and print the route table of one guided step.
 
     python tools/generate_bench.py [--model synthetic-sd15] [--size 512] [--steps 10] [--n 4] [--rounds 3] [--tokens 77] [--json FILE]
+                                   [--sampler ddim|dpm++2m|dpm++2m-sde [--eta 0] [--sampler-steps K]] [--variants A,G1]
 
 Every timed call ends in a device synchronise (the uint8 image is copied to the host); every shape is warmed up once before the
 timed rounds; the variants run alternately inside each round, so a drift of the machine shows up as spread, not as a difference.
@@ -10,6 +11,9 @@ timed rounds; the variants run alternately inside each round, so a drift of the 
   B  one call with n images, unguided
   G1 / Gn      guided (uncond and cond of equal length: one UNet forward of 2 / 2n rows per step), 1 image / n images
   G1_two       guided, 1 image, uncond one token shorter than cond: two forwards of 1 row per step
+`--sampler NAME`: every variant is timed a second time as `<variant>@NAME/K`, sampled by NAME in K = `--sampler-steps` steps (default:
+`--steps`), in turn with the default call at `--steps` -- e.g. `--steps 50 --sampler dpm++2m --sampler-steps 20 --n 1 --variants A,G1`
+times the 20-step DPM-Solver++ image against the 50-step DDIM image, unguided and guided.  `--variants`: only these.
 Times are per image."""
 import argparse
 import json
@@ -30,6 +34,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tokens", type=int, default=77)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--sampler", default=None, choices=("ddim", "dpm++2m", "dpm++2m-sde"))
+    ap.add_argument("--eta", type=float, default=0.0)
+    ap.add_argument("--sampler-steps", type=int, default=None)
+    ap.add_argument("--variants", default=None)
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "generate_bench.py measures the GPU path only"
@@ -48,20 +56,34 @@ def main():
 
     def single(**extra):
         for gen in gens(0, a.n):
-            ptp_utils.text2image_ldm_stable(ldm, cond, ctrl, generator=gen, **extra, **kw)
+            ptp_utils.text2image_ldm_stable(ldm, cond, ctrl, generator=gen, **{**kw, **extra})
         return a.n
 
     def batched(count, **extra):
-        ptp_utils.text2image_ldm_stable(ldm, cond, ctrl, generator=gens(0, count), **extra, **kw)
+        ptp_utils.text2image_ldm_stable(ldm, cond, ctrl, generator=gens(0, count), **{**kw, **extra})
         return count
     guide = dict(uncond_embedding=unc, guidance_scale=7.5)
-    variants = {
-        "A": lambda: single(),
-        "B": lambda: batched(a.n),
-        "G1": lambda: batched(1, **guide),
-        "Gn": lambda: batched(a.n, **guide),
-        "G1_two": lambda: batched(1, uncond_embedding=unc[:, :-1], guidance_scale=7.5),
-    }
+
+    def make(**over):
+        """The variants, with `over` on top of every call's keywords."""
+        return {
+            "A": lambda: single(**over),
+            "B": lambda: batched(a.n, **over),
+            "G1": lambda: batched(1, **guide, **over),
+            "Gn": lambda: batched(a.n, **guide, **over),
+            "G1_two": lambda: batched(1, uncond_embedding=unc[:, :-1], guidance_scale=7.5, **over),
+        }
+    variants = make()
+    names = a.variants.split(",") if a.variants else list(variants)
+    unknown = [k for k in names if k not in variants]
+    if unknown or not names:
+        ap.error(f"--variants: unknown {unknown}; choose from {list(variants)}")
+    variants = {k: variants[k] for k in names}
+    if a.sampler is not None:
+        k_steps = a.sampler_steps or a.steps
+        named = make(sampler=a.sampler, eta=a.eta, num_inference_steps=k_steps)
+        variants = {name: fn for k in names for name, fn in ((k, variants[k]), (f"{k}@{a.sampler}/{k_steps}", named[k]))}
+    width = max([7] + [len(k) for k in variants])
     times = {k: [] for k in variants}
     for k, fn in variants.items():                              # warm-up: every shape once
         fn()
@@ -75,7 +97,7 @@ def main():
             times[k].append((time.perf_counter() - t0) / images)
     print(f"{a.model} at {a.size}^2, {a.steps} steps, n = {a.n}, {a.tokens} tokens, {a.rounds} rounds; seconds per image")
     for k, ts in times.items():
-        print(f"  {k:7s} median {sorted(ts)[len(ts) // 2]:.4f}   min {min(ts):.4f}   max {max(ts):.4f}   all {[round(t, 4) for t in ts]}")
+        print(f"  {k:{width}s} median {sorted(ts)[len(ts) // 2]:.4f}   min {min(ts):.4f}   max {max(ts):.4f}   all {[round(t, 4) for t in ts]}")
     # routes of ONE guided step (2 rows) and of one guided step of n images (2n rows)
     tables = {}
     t = ldm.scheduler.timesteps[0]

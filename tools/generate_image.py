@@ -4,6 +4,7 @@
     python tools/generate_image.py --model <checkpoint dir | synthetic-sd15 | tiny> (--embedding emb.pt | --prompt TEXT) --out out/img
                                    [--steps 50] [--seed 0] [--n 1] [--size 512] [--device cuda]
                                    [--uncond unc.pt | --negative-prompt TEXT] [--guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
+                                   [--sampler ddim|dpm++2m|dpm++2m-sde] [--eta 0]
 
 `--embedding`: a tensor [1, T, D] (or [T, D]) saved with torch.save -- what `optimize_embedding` returns.  Image i is sampled from
 seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3]).
@@ -13,7 +14,10 @@ seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy
 `--negative-prompt TEXT`: the unconditional side as a prompt (the empty string is valid and means CLIP("")).  Either one loads the
 text encoder and its tokenizer with the model (tools/encode_prompt.py writes the same embeddings to files).
 `--batch B`: B images per sampling call (the seeds, the images' starting noise and the file names do not depend on it).
-`--prediction-type`: what the UNet predicts; default: the checkpoint's scheduler/scheduler_config.json, else epsilon."""
+`--prediction-type`: what the UNet predicts; default: the checkpoint's scheduler/scheduler_config.json, else epsilon.
+`--sampler`: ddim (the default), dpm++2m (DPM-Solver++ 2M: try `--steps 20`) or dpm++2m-sde; `--eta` in (0, 1] adds DDIM's variance
+noise (it selects ddim when `--sampler` is not given, and is an error with another sampler);
+the stochastic ones draw their noise from the image's seed, after its starting noise, so an image does not depend on `--batch`."""
 import argparse
 import os
 import sys
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--guidance", type=float, default=7.5)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--prediction-type", default=None, choices=("epsilon", "v_prediction", "sample"))
+    ap.add_argument("--sampler", default=None, choices=("ddim", "dpm++2m", "dpm++2m-sde"))
+    ap.add_argument("--eta", type=float, default=0.0)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -58,6 +64,12 @@ def main():
         unc = unc[None] if unc.dim() == 2 else unc
     if a.batch < 1:
         ap.error("--batch must be at least 1")
+    if not 0.0 <= a.eta <= 1.0:
+        ap.error("--eta must be in [0, 1]")
+    if a.eta > 0:
+        if a.sampler not in (None, "ddim"):
+            ap.error("--eta belongs to --sampler ddim")
+        a.sampler = "ddim"
     ldm, controllers, _ = load_ldm(a.device, a.model, decoder=True, prediction_type=a.prediction_type,
                                    text_encoder=a.prompt is not None or a.negative_prompt is not None)
     if emb is None:
@@ -74,7 +86,7 @@ def main():
         gens = [torch.Generator().manual_seed(a.seed + i) for i in ids]
         image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps, guidance_scale=a.guidance,
                                                    generator=gens[0] if a.batch == 1 else gens, height=a.size, width=a.size,
-                                                   uncond_embedding=unc, uncond_prompt=a.negative_prompt)
+                                                   uncond_embedding=unc, uncond_prompt=a.negative_prompt, sampler=a.sampler, eta=a.eta)
         for row, i in enumerate(ids):
             path = f"{a.out}_{i}" + (".png" if Image is not None else ".npy")
             if Image is not None:
