@@ -4,8 +4,8 @@
 // -> GroupNorm -> SiLU  as 4-5 separate full passes over the activation (ATen: RowwiseMoments, the GN apply
 // kernel, silu, broadcast adds); at B=8, 512^2 the VAE activations are 1 GB each and ATen's statistics kernel
 // gets one workgroup per (sample, group) = 256 workgroups => ~1.2 TB/s (profiles/).  Here:
-//   stats  : every (sample, group) row is split over `nsplit` workgroups (float4 loads, shifted sums so that
-//            E[(x-K)^2] - E[x-K]^2 does not cancel), partials combined in fp64 by the consumer
+//   stats  : every (sample, group) row is split over `nsplit` workgroups (float4 loads, sums shifted by a value typical
+//            of the split), the splits merged in fp64 by the consumer (mean, then a sum of squares about it)
 //   apply  : y = act( ((x + off[n,c]) - mean) * rstd * gamma[c] + beta[c] ),  act = SiLU or identity
 //   bwd    : dz = dy * act'(z);  dx = rstd * (g - mean_grp(g) - xhat * mean_grp(g * xhat)),  g = dz * gamma[c]
 // HBM-bound: 1 read for stats + 1 read + 1 write for apply (3 passes instead of 5+).
@@ -19,7 +19,10 @@ struct GNArgs {
     long L;              // elements per (sample, group) row = (C/G) * HW
 };
 
-// partial[(row * nsplit + split) * 3 + {0,1,2}] = {K, sum(v-K), sum((v-K)^2)} over this split's elements
+// partial[(row * nsplit + split) * 3 + {0,1,2}] = {K, sum(v-K), sum((v-K)^2)} over this split's elements.  The shift K is the
+// split's OWN: the mean of its first 256 float4 (one per thread), so a single odd element -- a hot corner pixel at x[row][0] --
+// cannot make it atypical of what is summed: with K = x[row][0] = 1000 on a row of N(0,1) the fp32 sums carried 1e6 per element
+// and the variance lost 3-4 digits.
 __global__ __launch_bounds__(256) void skp_gn_stats_kernel(GNArgs a, float* __restrict__ partial) {
     __shared__ float red[4];
     const int row = blockIdx.y, split = blockIdx.x, tid = threadIdx.x;
@@ -29,10 +32,22 @@ __global__ __launch_bounds__(256) void skp_gn_stats_kernel(GNArgs a, float* __re
     const long q4 = a.L / 4;                                   // HW % 4 == 0 is required by the launcher
     const long per = (q4 + a.nsplit - 1) / a.nsplit;
     const long lo = split * per, hi = (lo + per < q4) ? lo + per : q4;
-    const float K = xr[0] + (offr ? offr[0] : 0.f);
-    float s1 = 0.f, s2 = 0.f;
     const int hw4 = a.HW / 4;
-    for (long i = lo + tid; i < hi; i += 256) {
+    const long i0 = lo + tid;
+    f32x4 v0 = {0.f, 0.f, 0.f, 0.f};
+    if (i0 < hi) {
+        v0 = *(const f32x4*)(xr + i0 * 4);
+        if (offr) v0 += offr[i0 / hw4];
+    }
+    const long head = hi - lo < 256 ? hi - lo : 256;           // float4 that went into K (<= 0: an empty split, never merged)
+    const float K = skp_block_sum_256((v0[0] + v0[1]) + (v0[2] + v0[3]), red) / (float)(4 * (head > 0 ? head : 1));
+    float s1 = 0.f, s2 = 0.f;
+    if (i0 < hi) {
+        v0 -= K;
+        s1 = (v0[0] + v0[1]) + (v0[2] + v0[3]);
+        s2 = (v0[0] * v0[0] + v0[1] * v0[1]) + (v0[2] * v0[2] + v0[3] * v0[3]);
+    }
+    for (long i = i0 + 256; i < hi; i += 256) {
         f32x4 v = *(const f32x4*)(xr + i * 4);
         if (offr) v += offr[i / hw4];
         v -= K;
@@ -47,18 +62,30 @@ __global__ __launch_bounds__(256) void skp_gn_stats_kernel(GNArgs a, float* __re
     }
 }
 
+// The splits of a row merged in fp64, the row mean first and then  M2 = sum_s sum_i ((v_i - K_s) + (K_s - mean))^2
+// = sum_s [s2_s + e_s (2 s1_s + n_s e_s)],  e_s = K_s - mean: a sum of squares again, no difference of large sums (as
+// skp_gn_from_blocks_kernel merges its blocks); the element count n_s of a split follows from its index.
 __device__ __forceinline__ void skp_gn_finalize(const float* partial, int row, int nsplit, long L, float eps,
                                                 float& mean, float& rstd) {
-    double s1 = 0.0, s2 = 0.0;
-    const float K = partial[(size_t)row * nsplit * 3];
+    const long q4 = L / 4, per = (q4 + nsplit - 1) / nsplit;
+    const float* p = partial + (size_t)row * nsplit * 3;
+    double t = 0.0;
     for (int i = 0; i < nsplit; ++i) {
-        const float* p = partial + ((size_t)row * nsplit + i) * 3;
-        s1 += (double)p[1]; s2 += (double)p[2];
+        const long lo = i * per, hi = (lo + per < q4) ? lo + per : q4;
+        if (hi > lo) t += (double)(4 * (hi - lo)) * (double)p[3 * i] + (double)p[3 * i + 1];
     }
-    const double m = s1 / (double)L;
-    double var = s2 / (double)L - m * m;
+    const double m = t / (double)L;
+    double m2 = 0.0;
+    for (int i = 0; i < nsplit; ++i) {
+        const long lo = i * per, hi = (lo + per < q4) ? lo + per : q4;
+        if (hi > lo) {
+            const double e = (double)p[3 * i] - m;
+            m2 += (double)p[3 * i + 2] + e * (2.0 * (double)p[3 * i + 1] + (double)(4 * (hi - lo)) * e);
+        }
+    }
+    double var = m2 / (double)L;
     var = var < 0.0 ? 0.0 : var;
-    mean = (float)((double)K + m);
+    mean = (float)m;
     rstd = (float)(1.0 / sqrt(var + (double)eps));
 }
 
@@ -106,6 +133,20 @@ __global__ __launch_bounds__(256) void skp_gn_from_blocks_kernel(GNArgs a, const
     }
 }
 
+// The shift of  y = x * sc + (beta + dm * sc),  dm = off - mean,  as an unevaluated sum hi + lo: hi is the correctly rounded shift
+// (one fma), lo what that rounding lost (two-sum of beta and the product, plus the product's own residual).  The rounding of the
+// shift alone is |dm * sc| * 2^-24, and on a row of zero variance sc = gamma / sqrt(eps) is 316 ... 1000 x gamma: a row of 3.0
+// came out 1e-4 ... 2e-3 off beta; with lo added after the multiply-add it comes out within an ulp.  lo is kept only where
+// the mean is more than 16 standard deviations from zero: below that it is under 1e-6 of the row's scale (the order of what an
+// fp32 mean costs anyway), and without it the arithmetic is the reference implementation's own (torch's GroupNorm folds the
+// mean into the shift in the same way), which the trajectory tests hold the product to within 0.12 of a learning-rate step.
+__device__ __forceinline__ void skp_gn_shift(float dm, float rstd, float sc, float bet, float& hi, float& lo) {
+    const float p = __fmul_rn(dm, sc), pl = fmaf(dm, sc, -p);
+    const float s = __fadd_rn(bet, p), bb = s - bet, err = (bet - (s - bb)) + (p - bb);
+    hi = fmaf(dm, sc, bet);
+    lo = fabsf(dm) * rstd > 16.f ? ((s - hi) + err) + pl : 0.f;
+}
+
 // partial == nullptr: mean / rstd were produced by skp_gn_from_blocks_kernel (read, not written)
 __global__ __launch_bounds__(256) void skp_gn_apply_kernel(GNArgs a, const float* __restrict__ partial,
                                                            float* __restrict__ y, float* __restrict__ mean_out,
@@ -126,9 +167,11 @@ __global__ __launch_bounds__(256) void skp_gn_apply_kernel(GNArgs a, const float
     for (long i = (long)blockIdx.x * 256 + tid; i < q4; i += (long)gridDim.x * 256) {
         const int cl = (int)(i / hw4), c = g * Cg + cl;
         const float sc = rstd * a.gamma[c];
-        const float sh = a.beta[c] + ((a.off ? a.off[(size_t)n * a.C + c] : 0.f) - mean) * sc;
+        float sh, lo;
+        skp_gn_shift((a.off ? a.off[(size_t)n * a.C + c] : 0.f) - mean, rstd, sc, a.beta[c], sh, lo);
         f32x4 v = *(const f32x4*)(xr + i * 4);
         v = v * sc + sh;
+        v += lo;
         if (a.silu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + __expf(-v[e]));
@@ -282,8 +325,10 @@ __global__ __launch_bounds__(1024) void skp_gn_onepass_fwd_kernel(GNArgs a, floa
         if (i < q4) {
             const int c = g * Cg + i / hw4;
             const float sc = rstd * a.gamma[c];
-            const float sh = a.beta[c] - mean * sc;             // the offset is already inside v
+            float sh, lo;
+            skp_gn_shift(-mean, rstd, sc, a.beta[c], sh, lo);         // the offset is already inside v
             f32x4 r = v[j] * sc + sh;
+            r += lo;
             if (a.silu) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[e] = r[e] / (1.0f + __expf(-r[e]));
