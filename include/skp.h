@@ -445,10 +445,10 @@ int skp_conv3x3_small_out_f32(const void* x, const void* w, const void* bias, vo
                               int image, void* stream);
 
 /* y[i] = a * x[i] + b * z[i] for i < n (y may alias x or z): the eta = 0 DDIM update x_prev = c1 x_t + c2 eps with the two
- * coefficients computed on the host (ldm/scheduler.py DDIMScheduler.step). */
+ * coefficients computed on the host (skp_sampler_step.hip; ldm/scheduler.py DDIMScheduler.step). */
 int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, float b, void* stream);
 
-/* The guided DDIM update of the sampling loop in one pass (skp_ddim_step.hip; ldm/scheduler.py DDIMScheduler.step with
+/* The guided DDIM update of the sampling loop in one pass (skp_sampler_step.hip; ldm/scheduler.py DDIMScheduler.step with
  * `uncond_output`, a prediction type other than epsilon, or clipping).  Per element i < n:
  *   m         = m_u ? m_u + guidance * (m_c - m_u) : m_c                 (classifier-free guidance; m_u may be NULL)
  *   (x0, eps) = prediction 0 (epsilon): ((x - sb m) / sa, m)
@@ -486,7 +486,7 @@ int skp_sampler_step_f32(const float* x, const float* m_c, const float* m_u, con
 
 /* Image to bytes (ptp_utils.py `latent2image`): x float [B,3,H,W] in [0, 1] (the decoder's image epilogue) -> y uint8 [B,H,W,3],
  * y = (unsigned char)(x * 255.0f), truncating, no clamp: exactly what the host expression (x.permute(0,2,3,1) * 255).astype(uint8)
- * gives.  Any H, W (four pixels per lane when H * W % 4 == 0, one otherwise). */
+ * gives.  Any H, W (four pixels per lane when H * W % 4 == 0, one otherwise).  skp_conv_out.hip. */
 int skp_image_u8_nhwc_f32(const float* x, unsigned char* y, int B, int H, int W, void* stream);
 
 /* GEGLU of the transformer feed-forward (diffusers attention.GEGLU [third party], inside the hooked UNet forward):

@@ -22,6 +22,16 @@ static inline int skp_launch_status() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// Launch shape of the small memory-bound elementwise kernels (sampling step, image to bytes): 256-thread workgroups over a
+// grid-stride loop, the grid capped at 2048 workgroups.
+constexpr int SKP_EW_BLOCK = 256;
+constexpr long long SKP_EW_MAX_BLOCKS = 2048;
+inline unsigned skp_capped_grid(long long items) {
+    const long long blocks = (items + SKP_EW_BLOCK - 1) / SKP_EW_BLOCK;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > SKP_EW_MAX_BLOCKS ? SKP_EW_MAX_BLOCKS : blocks));
+}
+inline bool skp_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // (a null pointer counts as aligned)
+
 // PyTorch upsample_bicubic2d taps (align_corners=False, A=-0.75): source coordinate is NOT
 // clamped for cubic mode; tap indices are clamped to [0, n-1] on access.
 __device__ __forceinline__ void skp_cubic_taps(int dst, float ratio, int n, int idx[4], float w[4]) {

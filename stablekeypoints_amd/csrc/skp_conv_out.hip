@@ -5,7 +5,10 @@
 //   (zero padding by predication: one 8-byte load and two edge loads per row) and multiplied by the channel's 9 * Cout
 //   weights, which are wave-uniform (scalar loads, one SGPR operand per packed fma).
 // Optional image epilogue: clamp(y / 2 + 0.5, 0, 1), the [-1, 1] -> [0, 1] map of `latent2image`.  NCHW in and out, bias folded in.
-// Also here: the DDIM update of the sampling loop, x_prev = c1 x + c2 eps with host-computed coefficients.
+// Also here, the rest of the decoder's way out to the image:
+//   skp_image_u8_nhwc_f32   float [B,3,H,W] in [0, 1] -> uint8 [B,H,W,3], so that what crosses to the host is bytes.  16-byte loads
+//                           where the plane size and the pointers allow, a scalar form otherwise, the grid capped at 2048 workgroups
+//                           with a grid-stride loop.
 #include "skp_common.h"
 
 namespace {
@@ -74,10 +77,42 @@ __global__ __launch_bounds__(256) void skp_conv_out_kernel(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void skp_axpby_kernel(const float* __restrict__ x, const float* __restrict__ z,
-                                                        float* __restrict__ y, long long n, float ca, float cb) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] = ca * x[i] + cb * z[i];
+// One lane = four horizontally consecutive pixels of one image: three 16-byte loads (one per channel plane), twelve bytes out as
+// three dwords.  Needs H * W % 4 == 0 (every plane then starts 16-byte aligned, every group of four pixels 4-byte aligned in y).
+__device__ __forceinline__ unsigned u8_of(float v) { return (unsigned)(int)(v * 255.0f) & 0xffu; }
+
+__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_image_u8_vec_kernel(const float* __restrict__ x, unsigned* __restrict__ y,
+                                                                        long long plane4, long long total) {
+    const long long stride = (long long)gridDim.x * SKP_EW_BLOCK;
+    for (long long i = (long long)blockIdx.x * SKP_EW_BLOCK + threadIdx.x; i < total; i += stride) {
+        const long long b = i / plane4, q = i - b * plane4;
+        const f32x4* xb = (const f32x4*)x + b * 3 * plane4 + q;
+        const f32x4 r = xb[0], g = xb[plane4], bl = xb[2 * plane4];
+        unsigned px[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            px[3 * k] = u8_of(r[k]);
+            px[3 * k + 1] = u8_of(g[k]);
+            px[3 * k + 2] = u8_of(bl[k]);
+        }
+        unsigned* yo = y + i * 3;
+#pragma unroll
+        for (int w = 0; w < 3; ++w) yo[w] = px[4 * w] | (px[4 * w + 1] << 8) | (px[4 * w + 2] << 16) | (px[4 * w + 3] << 24);
+    }
+}
+
+// Any H, W: one lane = one pixel, three byte stores.
+__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_image_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ y,
+                                                                    long long plane, long long total) {
+    const long long stride = (long long)gridDim.x * SKP_EW_BLOCK;
+    for (long long i = (long long)blockIdx.x * SKP_EW_BLOCK + threadIdx.x; i < total; i += stride) {
+        const long long b = i / plane, p = i - b * plane;
+        const float* xb = x + b * 3 * plane + p;
+        unsigned char* yo = y + i * 3;
+        yo[0] = (unsigned char)u8_of(xb[0]);
+        yo[1] = (unsigned char)u8_of(xb[plane]);
+        yo[2] = (unsigned char)u8_of(xb[2 * plane]);
+    }
 }
 
 }  // namespace
@@ -100,11 +135,15 @@ extern "C" int skp_conv3x3_small_out_f32(const void* x, const void* w, const voi
     return skp_launch_status();
 }
 
-// y[i] = a * x[i] + b * z[i], i < n (y may be x or z).  The eta = 0 DDIM update with clip_sample off is exactly this.
-extern "C" int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, float b, void* stream) {
-    if (!x || !z || !y || n <= 0) return SKP_E_BADARG;
-    if (n > (int64_t)0x7fffffff * 256) return SKP_E_RANGE;
-    hipLaunchKernelGGL(skp_axpby_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       (const float*)z, (float*)y, (long long)n, a, b);
+extern "C" int skp_image_u8_nhwc_f32(const float* x, unsigned char* y, int B, int H, int W, void* stream) {
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0) return SKP_E_BADARG;
+    const long long plane = (long long)H * W, total = plane * B;
+    hipStream_t st = (hipStream_t)stream;
+    if ((plane & 3) == 0 && skp_aligned16(x) && ((uintptr_t)y & 3) == 0) {
+        hipLaunchKernelGGL(skp_image_u8_vec_kernel, dim3(skp_capped_grid(total / 4)), dim3(SKP_EW_BLOCK), 0, st, x, (unsigned*)y,
+                           plane / 4, total / 4);
+    } else {
+        hipLaunchKernelGGL(skp_image_u8_kernel, dim3(skp_capped_grid(total)), dim3(SKP_EW_BLOCK), 0, st, x, y, plane, total);
+    }
     return skp_launch_status();
 }

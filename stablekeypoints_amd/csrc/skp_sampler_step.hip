@@ -1,25 +1,39 @@
-// The step of the image-sampling loop for the samplers of ldm/samplers.py (stochastic DDIM, DPM-Solver++(2M), SDE-DPM-Solver++(2M)):
-//   skp_sampler_step_f32    classifier-free guidance mix + (x0, eps) for epsilon / v / sample prediction + the optional x0 clamp +
-//                           y = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise in one pass; y may be written twice (the duplicated
-//                           UNet input of the next guided step) and the clamped x0 is kept for the next step's x0_prev.
-// Built like skp_ddim_step.hip: memory-bound and tiny (a latent is 16 K floats), 16-byte accesses where pointers and counts allow, a
-// scalar form otherwise, the grid capped at 2048 workgroups with a grid-stride loop.  Every output element is computed by the lane
-// that read its inputs, after reading them, which is what makes y == x and x0_out == x0_prev legal.
+// The step of the image-sampling loop (ptp_utils.py `text2image_ldm_stable`), one kernel behind two entries:
+//   skp_ddim_step_f32       classifier-free guidance mix + (x0, eps) for epsilon / v / sample prediction + the optional x0 clamp +
+//                           the eta = 0 DDIM update y = pa x0 + pb eps (ldm/scheduler.py `DDIMScheduler.step`);
+//   skp_sampler_step_f32    the same up to the clamp, then y = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise for the samplers of
+//                           ldm/samplers.py (stochastic DDIM, DPM-Solver++(2M), SDE-DPM-Solver++(2M)); the clamped x0 is kept for
+//                           the next step's x0_prev.
+// Either may write y twice (the duplicated UNet input of the next guided step, so the loop needs no concatenation).
+// Memory-bound and tiny (a latent is 16 K floats): 16-byte accesses where pointers and counts allow, a scalar form otherwise, the grid
+// capped at 2048 workgroups with a grid-stride loop.  Every output element is computed by the lane that read its inputs, after
+// reading them, which is what makes y == x and x0_out == x0_prev legal.
+// Also here: skp_axpby_f32, the plain unguided epsilon form of the DDIM update, x_prev = c1 x + c2 eps with host-computed coefficients.
 #include "skp_common.h"
 
 namespace {
 
-constexpr int SAMP_BLOCK = 256;
-constexpr long long SAMP_MAX_BLOCKS = 2048;
-
-struct SamplerCoef {
-    float g, sa, sb, cx, c0, ce, c1, cn;
+struct StepCoef {
+    float g, sa, sb, cx, c0, ce, c1, cn;                            // cx, c1, cn: FULL only
     int prediction, clip;
 };
 
+// What only the FULL (sampler) form takes, each may be null; the DDIM form carries no such arguments.
+template <bool FULL>
+struct StepExtra {
+    const float *x0_prev, *noise;
+    float* x0_out;
+};
+template <>
+struct StepExtra<false> {
+    static constexpr const float *x0_prev = nullptr, *noise = nullptr;
+    static constexpr float* x0_out = nullptr;
+};
+
 // -> y; x0 (after the clamp) through `x0c`.  `p` / `nz` are 0 where x0_prev / noise are absent (their coefficients are 0 then).
-template <bool GUIDED>
-__device__ __forceinline__ float sampler_one(float x, float mc, float mu, float p, float nz, const SamplerCoef& c, float& x0c) {
+// The DDIM form is an expression of its own, not the five terms with zeros: the two contract into different fused multiply-adds.
+template <bool GUIDED, bool FULL>
+__device__ __forceinline__ float step_one(float x, float mc, float mu, float p, float nz, const StepCoef& c, float& x0c) {
     const float m = GUIDED ? mu + c.g * (mc - mu) : mc;
     float x0, eps;
     if (c.prediction == 0) {
@@ -34,20 +48,23 @@ __device__ __forceinline__ float sampler_one(float x, float mc, float mu, float 
     }
     if (c.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     x0c = x0;
-    return c.cx * x + c.c0 * x0 + c.ce * eps + c.c1 * p + c.cn * nz;
+    if (FULL) return c.cx * x + c.c0 * x0 + c.ce * eps + c.c1 * p + c.cn * nz;
+    return c.c0 * x0 + c.ce * eps;
 }
 
 // VEC: every pointer given is 16-byte aligned; groups of four elements per lane, the n % 4 tail by the first lanes of workgroup 0.
 // Y2VEC: the second copy y + n is 16-byte aligned too (n % 4 == 0); otherwise it is written with scalar stores.
-// x / y and x0_prev / x0_out carry no __restrict__: each pair may be one buffer.  x0_prev, noise and x0_out may be null.
-template <bool GUIDED, bool VEC, bool Y2VEC>
-__global__ __launch_bounds__(SAMP_BLOCK) void skp_sampler_step_kernel(const float* x, const float* __restrict__ mc,
-                                                                      const float* __restrict__ mu, const float* x0_prev,
-                                                                      const float* __restrict__ noise, float* y, float* x0_out,
-                                                                      long long n, int copies, SamplerCoef c) {
-    const long long tid = (long long)blockIdx.x * SAMP_BLOCK + threadIdx.x;
-    const long long stride = (long long)gridDim.x * SAMP_BLOCK;
+// x / y and x0_prev / x0_out carry no __restrict__: each pair may be one buffer.
+template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL>
+__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const float* x, const float* __restrict__ mc,
+                                                                        const float* __restrict__ mu, StepExtra<FULL> e, float* y,
+                                                                        long long n, int copies, StepCoef c) {
+    const long long tid = (long long)blockIdx.x * SKP_EW_BLOCK + threadIdx.x;
+    const long long stride = (long long)gridDim.x * SKP_EW_BLOCK;
     float* y2 = copies == 2 ? y + n : nullptr;
+    const float* x0_prev = e.x0_prev;
+    const float* __restrict__ noise = e.noise;
+    float* x0_out = e.x0_out;
     if (VEC) {
         const long long n4 = n >> 2;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -61,7 +78,7 @@ __global__ __launch_bounds__(SAMP_BLOCK) void skp_sampler_step_kernel(const floa
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float x0c;
-                r[k] = sampler_one<GUIDED>(xv[k], cv[k], uv[k], pv[k], nv[k], c, x0c);
+                r[k] = step_one<GUIDED, FULL>(xv[k], cv[k], uv[k], pv[k], nv[k], c, x0c);
                 z[k] = x0c;
             }
             ((f32x4*)y)[i] = r;
@@ -78,8 +95,8 @@ __global__ __launch_bounds__(SAMP_BLOCK) void skp_sampler_step_kernel(const floa
         const long long t = (n4 << 2) + tid;                        // tail: at most three elements
         if (tid < 4 && t < n) {
             float x0c;
-            const float r = sampler_one<GUIDED>(x[t], mc[t], GUIDED ? mu[t] : 0.f, x0_prev ? x0_prev[t] : 0.f,
-                                                noise ? noise[t] : 0.f, c, x0c);
+            const float r = step_one<GUIDED, FULL>(x[t], mc[t], GUIDED ? mu[t] : 0.f, x0_prev ? x0_prev[t] : 0.f,
+                                                   noise ? noise[t] : 0.f, c, x0c);
             y[t] = r;
             if (y2) y2[t] = r;
             if (x0_out) x0_out[t] = x0c;
@@ -87,8 +104,8 @@ __global__ __launch_bounds__(SAMP_BLOCK) void skp_sampler_step_kernel(const floa
     } else {
         for (long long i = tid; i < n; i += stride) {
             float x0c;
-            const float r = sampler_one<GUIDED>(x[i], mc[i], GUIDED ? mu[i] : 0.f, x0_prev ? x0_prev[i] : 0.f,
-                                                noise ? noise[i] : 0.f, c, x0c);
+            const float r = step_one<GUIDED, FULL>(x[i], mc[i], GUIDED ? mu[i] : 0.f, x0_prev ? x0_prev[i] : 0.f,
+                                                   noise ? noise[i] : 0.f, c, x0c);
             y[i] = r;
             if (y2) y2[i] = r;
             if (x0_out) x0_out[i] = x0c;
@@ -96,14 +113,51 @@ __global__ __launch_bounds__(SAMP_BLOCK) void skp_sampler_step_kernel(const floa
     }
 }
 
-inline unsigned capped_grid(long long items) {
-    const long long blocks = (items + SAMP_BLOCK - 1) / SAMP_BLOCK;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > SAMP_MAX_BLOCKS ? SAMP_MAX_BLOCKS : blocks));
+// The alignment decision, the grid and the launch for both entries, which have checked their arguments.  `full`: the sampler form;
+// otherwise x0_prev, noise and x0_out are null and the kernel does not take them.
+int step_launch(bool full, const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise, float* y,
+                float* x0_out, int64_t n, int copies, const StepCoef& c, void* stream) {
+    const bool vec = skp_aligned16(x) && skp_aligned16(m_c) && skp_aligned16(m_u) && skp_aligned16(x0_prev) && skp_aligned16(noise) &&
+                     skp_aligned16(y) && skp_aligned16(x0_out) && n >= 4;
+    const bool y2vec = (n & 3) == 0;
+    const dim3 grid(skp_capped_grid(vec ? n / 4 : n)), block(SKP_EW_BLOCK);
+    hipStream_t st = (hipStream_t)stream;
+#define SKP_STEP_AS(G, V, Y2, FULL, ...)                                                                                       \
+    hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2, FULL>), grid, block, 0, st, x, m_c, m_u, StepExtra<FULL>{__VA_ARGS__}, y, \
+                       (long long)n, copies, c)
+#define SKP_STEP(G, V, Y2)                                             \
+    do {                                                               \
+        if (full) SKP_STEP_AS(G, V, Y2, true, x0_prev, noise, x0_out); \
+        else SKP_STEP_AS(G, V, Y2, false);                             \
+    } while (0)
+    if (m_u) {
+        if (!vec) SKP_STEP(true, false, false);
+        else if (y2vec) SKP_STEP(true, true, true);
+        else SKP_STEP(true, true, false);
+    } else {
+        if (!vec) SKP_STEP(false, false, false);
+        else if (y2vec) SKP_STEP(false, true, true);
+        else SKP_STEP(false, true, false);
+    }
+#undef SKP_STEP
+#undef SKP_STEP_AS
+    return skp_launch_status();
 }
 
-inline bool aligned16_or_null(const void* p) { return ((uintptr_t)p & 15) == 0; }
+__global__ __launch_bounds__(256) void skp_axpby_kernel(const float* __restrict__ x, const float* __restrict__ z,
+                                                        float* __restrict__ y, long long n, float ca, float cb) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = ca * x[i] + cb * z[i];
+}
 
 }  // namespace
+
+extern "C" int skp_ddim_step_f32(const float* x, const float* m_c, const float* m_u, float* y, int64_t n, int copies, float guidance,
+                                 int prediction, float sa, float sb, float pa, float pb, int clip, void* stream) {
+    if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
+    const StepCoef c{guidance, sa, sb, 0.f, pa, pb, 0.f, 0.f, prediction, clip ? 1 : 0};
+    return step_launch(false, x, m_c, m_u, nullptr, nullptr, y, nullptr, n, copies, c, stream);
+}
 
 extern "C" int skp_sampler_step_f32(const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise,
                                     float* y, float* x0_out, int64_t n, int copies, float guidance, int prediction, float sa,
@@ -112,24 +166,15 @@ extern "C" int skp_sampler_step_f32(const float* x, const float* m_c, const floa
     if ((c1 != 0.f && !x0_prev) || (cn != 0.f && !noise)) return SKP_E_BADARG;
     if (c1 == 0.f) x0_prev = nullptr;                               // not read: a buffer that holds no x0 yet may be anything, NaN included
     if (cn == 0.f) noise = nullptr;
-    const SamplerCoef c{guidance, sa, sb, cx, c0, ce, c1, cn, prediction, clip ? 1 : 0};
-    const bool vec = aligned16_or_null(x) && aligned16_or_null(m_c) && aligned16_or_null(m_u) && aligned16_or_null(x0_prev) &&
-                     aligned16_or_null(noise) && aligned16_or_null(y) && aligned16_or_null(x0_out) && n >= 4;
-    const bool y2vec = (n & 3) == 0;
-    const dim3 grid(capped_grid(vec ? n / 4 : n)), block(SAMP_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
-#define SKP_SAMP(G, V, Y2)                                                                                                    \
-    hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2>), grid, block, 0, st, x, m_c, m_u, x0_prev, noise, y, x0_out, (long long)n, \
-                       copies, c)
-    if (m_u) {
-        if (!vec) SKP_SAMP(true, false, false);
-        else if (y2vec) SKP_SAMP(true, true, true);
-        else SKP_SAMP(true, true, false);
-    } else {
-        if (!vec) SKP_SAMP(false, false, false);
-        else if (y2vec) SKP_SAMP(false, true, true);
-        else SKP_SAMP(false, true, false);
-    }
-#undef SKP_SAMP
+    const StepCoef c{guidance, sa, sb, cx, c0, ce, c1, cn, prediction, clip ? 1 : 0};
+    return step_launch(true, x, m_c, m_u, x0_prev, noise, y, x0_out, n, copies, c, stream);
+}
+
+// y[i] = a * x[i] + b * z[i], i < n (y may be x or z).  The eta = 0 DDIM update with clip_sample off is exactly this.
+extern "C" int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, float a, float b, void* stream) {
+    if (!x || !z || !y || n <= 0) return SKP_E_BADARG;
+    if (n > (int64_t)0x7fffffff * 256) return SKP_E_RANGE;
+    hipLaunchKernelGGL(skp_axpby_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)z, (float*)y, (long long)n, a, b);
     return skp_launch_status();
 }

@@ -33,11 +33,33 @@ class StepCoef(NamedTuple):
     """One step's host numbers, in the order `ops.sampler_step(coef=)` and skp_sampler_step_f32 take them."""
     sa: float
     sb: float
-    cx: float
+    cx: float                                # None: no `cx x` term at all (`step_formula`; host only)
     c0: float
     ce: float
     c1: float
     cn: float
+
+
+def step_formula(x, m_c, m_u, coef, guidance, prediction_type, clip, x0_prev=None, noise=None):
+    """The update at the top of this file in torch, in the dtype of its inputs -> (y, x0c): what the step kernel
+    (`ops.sampler_step`, `ops.ddim_step`) computes, for host tensors and other dtypes.  `m_u` None: no guidance.  A term whose tensor
+    is absent is not evaluated, and neither is `cx x` when `coef.cx` is None (the DDIM form y = c0 x0c + ce eps of
+    `DDIMScheduler.step`; a `0 * x` there would turn a -0 into +0 and an infinite x into NaN)."""
+    m = m_c if m_u is None else m_u + guidance * (m_c - m_u)
+    if prediction_type == "epsilon":
+        x0, eps = (x - coef.sb * m) / coef.sa, m
+    elif prediction_type == "v_prediction":
+        x0, eps = coef.sa * x - coef.sb * m, coef.sa * m + coef.sb * x
+    else:
+        x0, eps = m, (x - coef.sa * m) / coef.sb
+    if clip:
+        x0 = x0.clamp(-1, 1)
+    y = coef.c0 * x0 + coef.ce * eps if coef.cx is None else coef.cx * x + coef.c0 * x0 + coef.ce * eps
+    if x0_prev is not None:
+        y = y + coef.c1 * x0_prev
+    if noise is not None:
+        y = y + coef.cn * noise
+    return y, x0
 
 
 def is_stochastic(kind: str, eta: float = 0.0) -> bool:

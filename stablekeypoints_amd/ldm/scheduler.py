@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import torch
 
+from .samplers import StepCoef, step_formula
+
 
 PREDICTION_TYPES = ("epsilon", "v_prediction", "sample")
 
@@ -87,14 +89,6 @@ class DDIMScheduler:
             return {"prev_sample": ops.ddim_step(sample, model_output, uncond_output, sa=sa, sb=sb, pa=pa, pb=pb,
                                                  guidance=float(guidance_scale), prediction=self.prediction_type,
                                                  clip=self.clip_sample, copies=copies)}
-        m = uncond_output + guidance_scale * (model_output - uncond_output) if guided else model_output
-        if self.prediction_type == "epsilon":
-            x0, eps = (sample - sb * m) / sa, m
-        elif self.prediction_type == "v_prediction":
-            x0, eps = sa * sample - sb * m, sa * m + sb * sample
-        else:
-            x0, eps = m, (sample - sa * m) / sb
-        if self.clip_sample:
-            x0 = x0.clamp(-1, 1)
-        prev = pa * x0 + pb * eps
+        prev, _ = step_formula(sample, model_output, uncond_output, StepCoef(sa, sb, None, pa, pb, 0, 0), guidance_scale,
+                               self.prediction_type, self.clip_sample)
         return {"prev_sample": torch.cat([prev, prev]) if copies == 2 else prev}

@@ -1486,7 +1486,7 @@ def conv3x3_up2(x, weight, bias=None):
 
 
 def axpby(x, z, a: float, b: float):
-    """a * x + b * z in one pass (the DDIM update with host-computed coefficients)."""
+    """a * x + b * z in one pass (the DDIM update with host-computed coefficients; csrc/skp_sampler_step.hip)."""
     x, z = _dev(x, "x"), _dev(z, "z")
     if x.shape != z.shape:
         raise RuntimeError("axpby: shapes differ")
@@ -1498,27 +1498,37 @@ def axpby(x, z, a: float, b: float):
 DDIM_PREDICTION = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 
 
-def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, guidance: float = 1.0, prediction="epsilon",
-              clip: bool = False, copies: int = 1, out=None):
-    """The guided DDIM update in one pass (csrc/skp_ddim_step.hip, formula in include/skp.h): m = m_u + guidance (m_c - m_u) when
-    `m_u` is given, else m_c; (x0, eps) from (x, m) by `prediction` ("epsilon" | "v_prediction" | "sample" or 0 | 1 | 2); x0
-    clamped to [-1, 1] when `clip`; y = pa x0 + pb eps.  -> y shaped like x, or with `copies=2` like torch.cat([x, x]): the result
-    twice along dim 0.  `out`: a contiguous float32 tensor of copies * x.numel() elements to write into; it may be x itself, or
-    (copies = 2) a buffer whose first half x is."""
+def _step_args(who, x, m_c, m_u, x0_prev, noise, prediction, copies, out):
+    """What `ddim_step` and `sampler_step` share -> (x, m_c, m_u, noise, prediction as 0 | 1 | 2, x.numel(), out): the inputs as
+    contiguous float32 device tensors of one shape, and `out` allocated or validated."""
     x, m_c = _dev(x, "x"), _dev(m_c, "m_c")
     m_u = _dev(m_u, "m_u") if m_u is not None else None
-    if m_c.shape != x.shape or (m_u is not None and m_u.shape != x.shape):
-        raise RuntimeError("ddim_step: shapes differ")
+    noise = _dev(noise, "noise") if noise is not None else None
+    if x0_prev is not None and not (x0_prev.is_cuda and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous()):
+        raise RuntimeError(f"{who}: `x0_prev` must be a contiguous float32 device tensor")
+    if any(t is not None and t.shape != x.shape for t in (m_c, m_u, x0_prev, noise)):
+        raise RuntimeError(f"{who}: shapes differ")
     pred = DDIM_PREDICTION.get(prediction, prediction)
     if pred not in (0, 1, 2) or copies not in (1, 2):
-        raise ValueError(f"ddim_step: prediction {prediction!r} / copies {copies!r}")
+        raise ValueError(f"{who}: prediction {prediction!r} / copies {copies!r}")
     n = x.numel()
     if out is None:
         out = torch.empty((copies * x.shape[0],) + tuple(x.shape[1:]) if x.dim() else (copies,), device=x.device, dtype=torch.float32)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == copies * n):
-        raise RuntimeError("ddim_step: `out` must be a contiguous float32 device tensor of copies * x.numel() elements")
+        raise RuntimeError(f"{who}: `out` must be a contiguous float32 device tensor of copies * x.numel() elements")
+    return x, m_c, m_u, noise, int(pred), n, out
+
+
+def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, guidance: float = 1.0, prediction="epsilon",
+              clip: bool = False, copies: int = 1, out=None):
+    """The guided DDIM update in one pass (csrc/skp_sampler_step.hip, formula in include/skp.h): m = m_u + guidance (m_c - m_u) when
+    `m_u` is given, else m_c; (x0, eps) from (x, m) by `prediction` ("epsilon" | "v_prediction" | "sample" or 0 | 1 | 2); x0
+    clamped to [-1, 1] when `clip`; y = pa x0 + pb eps.  -> y shaped like x, or with `copies=2` like torch.cat([x, x]): the result
+    twice along dim 0.  `out`: a contiguous float32 tensor of copies * x.numel() elements to write into; it may be x itself, or
+    (copies = 2) a buffer whose first half x is."""
+    x, m_c, m_u, _, pred, n, out = _step_args("ddim_step", x, m_c, m_u, None, None, prediction, copies, out)
     N.check(N.lib().skp_ddim_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), out.data_ptr(), n, int(copies), float(guidance),
-                                      int(pred), float(sa), float(sb), float(pa), float(pb), int(bool(clip)), _stream()),
+                                      pred, float(sa), float(sb), float(pa), float(pb), int(bool(clip)), _stream()),
             "skp_ddim_step_f32")
     return out
 
@@ -1531,36 +1541,22 @@ def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: 
     `x0_prev` / `noise`: shaped like x; each may be None when its coefficient is 0.  `out`: as in `ddim_step` (it may be x, or
     a doubled buffer whose first half x is).  `x0_out`: a contiguous float32 tensor shaped like x that receives the clamped x0; it
     may be `x0_prev` itself (the history updated in place)."""
-    x, m_c = _dev(x, "x"), _dev(m_c, "m_c")
-    m_u = _dev(m_u, "m_u") if m_u is not None else None
-    noise = _dev(noise, "noise") if noise is not None else None
-    if x0_prev is not None and not (x0_prev.is_cuda and x0_prev.dtype == torch.float32 and x0_prev.is_contiguous()):
-        raise RuntimeError("sampler_step: `x0_prev` must be a contiguous float32 device tensor")
-    if any(t is not None and t.shape != x.shape for t in (m_c, m_u, x0_prev, noise)):
-        raise RuntimeError("sampler_step: shapes differ")
-    pred = DDIM_PREDICTION.get(prediction, prediction)
-    if pred not in (0, 1, 2) or copies not in (1, 2):
-        raise ValueError(f"sampler_step: prediction {prediction!r} / copies {copies!r}")
+    x, m_c, m_u, noise, pred, n, out = _step_args("sampler_step", x, m_c, m_u, x0_prev, noise, prediction, copies, out)
     sa, sb, cx, c0, ce, c1, cn = (float(v) for v in coef)
     if (c1 != 0.0 and x0_prev is None) or (cn != 0.0 and noise is None):
         raise ValueError("sampler_step: a nonzero c1 needs `x0_prev`, a nonzero cn needs `noise`")
-    n = x.numel()
-    if out is None:
-        out = torch.empty((copies * x.shape[0],) + tuple(x.shape[1:]) if x.dim() else (copies,), device=x.device, dtype=torch.float32)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == copies * n):
-        raise RuntimeError("sampler_step: `out` must be a contiguous float32 device tensor of copies * x.numel() elements")
     if x0_out is not None and not (x0_out.is_cuda and x0_out.dtype == torch.float32 and x0_out.is_contiguous()
                                    and x0_out.numel() == n):
         raise RuntimeError("sampler_step: `x0_out` must be a contiguous float32 device tensor of x.numel() elements")
     N.check(N.lib().skp_sampler_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), _ptr(x0_prev), _ptr(noise), out.data_ptr(),
-                                         _ptr(x0_out), n, int(copies), float(guidance), int(pred), sa, sb, cx, c0, ce, c1, cn,
+                                         _ptr(x0_out), n, int(copies), float(guidance), pred, sa, sb, cx, c0, ce, c1, cn,
                                          int(bool(clip)), _stream()), "skp_sampler_step_f32")
     return out
 
 
 def image_u8_nhwc(x):
     """float [B,3,H,W] in [0, 1] -> uint8 [B,H,W,3] = (x.permute(0, 2, 3, 1) * 255) truncated, on the device
-    (csrc/skp_ddim_step.hip; `ptp_utils.latent2image`)."""
+    (csrc/skp_conv_out.hip; `ptp_utils.latent2image`)."""
     x = _dev(x.detach(), "x")
     if x.dim() != 4 or x.shape[1] != 3:
         raise RuntimeError(f"image_u8_nhwc: expected [B,3,H,W], got {tuple(x.shape)}")

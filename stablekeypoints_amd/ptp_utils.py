@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from . import routes
+from .ldm.samplers import SamplerPlan, step_formula
 from .ldm.unet import StopForward
 from ._maps import FusedAttn, collect_maps
 
@@ -386,7 +387,7 @@ def latent2image(vae, latents):
 
 def _image2uint8(image):
     """float [B, 3, H, W] in [0, 1] -> uint8 numpy [B, H, W, 3], truncating.  A float32 device image is permuted and converted by
-    one kernel (csrc/skp_ddim_step.hip), so the copy to the host is bytes; the result is the host expression's, bit for bit."""
+    one kernel (csrc/skp_conv_out.hip), so the copy to the host is bytes; the result is the host expression's, bit for bit."""
     if image.is_cuda and image.dtype == torch.float32:
         routes.note("image.u8", "nhwc_u8")
         return ops.image_u8_nhwc(image).cpu().numpy()
@@ -429,6 +430,34 @@ def init_latents(latent, model, height, width, generators):
     return latent, latent.to(model.device)
 
 
+def _predict(model, latents, context, t, doubled):
+    """The UNet forward(s) of one sampling step -> (latents [n, C, h, w], pred_c, pred_u).  `context = [uncond, cond]`: `uncond`
+    None -- the conditional prediction alone (pred_u None); contexts of equal length -- ONE forward of 2n rows, the unconditional
+    rows first (`doubled`: `latents` already holds the n rows twice); otherwise two forwards of n rows."""
+    uncond, cond = context
+    if uncond is None:
+        return latents, _unet_forward_shared_context(model, latents, t, cond), None
+    if uncond.shape[1] != cond.shape[1]:
+        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
+        return latents, _unet_forward_shared_context(model, latents, t, cond), pred_u
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    rows = latents if doubled else torch.cat([latents, latents])
+    ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
+    pred = _unet_forward_shared_context(model, rows, t, ctx)
+    return rows[:n], pred[n:], pred[:n]
+
+
+def _finish(controller, out, doubled):
+    """`controller.step_callback` on the step's result -- on its first copy when `doubled`, duplicated again only if the callback
+    returned another tensor."""
+    if controller is not None:
+        first = out[:out.shape[0] // 2] if doubled else out
+        called = controller.step_callback(first)
+        if called is not first:
+            out = torch.cat([called, called]) if doubled else called
+    return out
+
+
 def guided_latent_step(model, controller, latents, context, t, guidance_scale, *, doubled=False):
     """One sampling step with classifier-free guidance: the branch of ptp_utils.py:337-349 that the reference's `low_resource=False`
     names, as an entry of its own (`latent_step` stays the conditional prediction alone).  `context = [uncond, cond]`, each [1, T, D];
@@ -443,27 +472,12 @@ def guided_latent_step(model, controller, latents, context, t, guidance_scale, *
     twice, so the loop of `text2image_ldm_stable` concatenates once before its first step and never after (GPU, equal T; the
     host route and contexts of different length concatenate or run two forwards per step).  Works in whatever dtype the module tree and its inputs have."""
     uncond, cond = context
-    same_t = uncond.shape[1] == cond.shape[1]
-    if doubled and not same_t:
+    if doubled and uncond.shape[1] != cond.shape[1]:
         raise ValueError("guided_latent_step: doubled latents need contexts of equal length")
-    n = latents.shape[0] // 2 if doubled else latents.shape[0]
-    if same_t:
-        rows = latents if doubled else torch.cat([latents, latents])
-        ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
-        pred = _unet_forward_shared_context(model, rows, t, ctx)
-        pred_u, pred_c = pred[:n], pred[n:]
-        latents = rows[:n]
-    else:
-        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
-        pred_c = _unet_forward_shared_context(model, latents, t, cond)
+    latents, pred_c, pred_u = _predict(model, latents, context, t, doubled)
     out = model.scheduler.step(pred_c, t, latents, uncond_output=pred_u, guidance_scale=guidance_scale,
                                copies=2 if doubled else 1)["prev_sample"]
-    if controller is not None:
-        first = out[:n] if doubled else out
-        called = controller.step_callback(first)
-        if called is not first:
-            out = torch.cat([called, called]) if doubled else called
-    return out
+    return _finish(controller, out, doubled)
 
 
 def latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True):
@@ -473,10 +487,7 @@ def latent_step(model, controller, latents, context, t, guidance_scale, low_reso
     if not low_resource:
         raise NotImplementedError("latent_step: only the low_resource branch (conditional prediction alone) is built")
     noise_pred = _unet_forward_shared_context(model, latents, t, context[1])
-    latents = model.scheduler.step(noise_pred, t, latents)["prev_sample"]
-    if controller is not None:
-        latents = controller.step_callback(latents)
-    return latents
+    return _finish(controller, model.scheduler.step(noise_pred, t, latents)["prev_sample"], False)
 
 
 def sampler_latent_step(model, controller, latents, context, t, guidance_scale, *, plan, coef, x0_hist, noise=None, doubled=False):
@@ -492,19 +503,7 @@ def sampler_latent_step(model, controller, latents, context, t, guidance_scale, 
     guided = uncond is not None
     if doubled and not (guided and uncond.shape[1] == cond.shape[1]):
         raise ValueError("sampler_latent_step: doubled latents need guidance with contexts of equal length")
-    n = latents.shape[0] // 2 if doubled else latents.shape[0]
-    pred_u = None
-    if guided and uncond.shape[1] == cond.shape[1]:
-        rows = latents if doubled else torch.cat([latents, latents])
-        ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
-        pred = _unet_forward_shared_context(model, rows, t, ctx)
-        pred_u, pred_c = pred[:n], pred[n:]
-        latents = rows[:n]
-    elif guided:
-        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
-        pred_c = _unet_forward_shared_context(model, latents, t, cond)
-    else:
-        pred_c = _unet_forward_shared_context(model, latents, t, cond)
+    latents, pred_c, pred_u = _predict(model, latents, context, t, doubled)
     prev = x0_hist if coef.c1 != 0 else None
     nz = noise if coef.cn != 0 else None
     if latents.is_cuda and all(v is None or v.dtype == torch.float32 for v in (latents, pred_c, pred_u, prev, nz, x0_hist)):
@@ -513,29 +512,11 @@ def sampler_latent_step(model, controller, latents, context, t, guidance_scale, 
                                prediction=plan.prediction_type, clip=plan.clip_sample, copies=2 if doubled else 1, x0_out=x0_hist)
     else:
         routes.note("sample.step", "host")
-        m = pred_u + guidance_scale * (pred_c - pred_u) if guided else pred_c
-        if plan.prediction_type == "epsilon":
-            x0, eps = (latents - coef.sb * m) / coef.sa, m
-        elif plan.prediction_type == "v_prediction":
-            x0, eps = coef.sa * latents - coef.sb * m, coef.sa * m + coef.sb * latents
-        else:
-            x0, eps = m, (latents - coef.sa * m) / coef.sb
-        if plan.clip_sample:
-            x0 = x0.clamp(-1, 1)
-        out = coef.cx * latents + coef.c0 * x0 + coef.ce * eps
-        if prev is not None:
-            out = out + coef.c1 * prev
-        if nz is not None:
-            out = out + coef.cn * nz
+        out, x0 = step_formula(latents, pred_c, pred_u, coef, guidance_scale, plan.prediction_type, plan.clip_sample, prev, nz)
         if x0_hist is not None:
             x0_hist.copy_(x0)
         out = torch.cat([out, out]) if doubled else out
-    if controller is not None:
-        first = out[:n] if doubled else out
-        called = controller.step_callback(first)
-        if called is not first:
-            out = torch.cat([called, called]) if doubled else called
-    return out
+    return _finish(controller, out, doubled)
 
 
 def _step_noise(plan, steps, latent, generator):
@@ -646,7 +627,6 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     if sampler is None and eta != 0:
         raise ValueError(f"eta = {eta!r} needs sampler=\"ddim\": without a sampler the call is the deterministic DDIM step")
     if sampler is not None:
-        from .ldm.samplers import SamplerPlan
         plan = SamplerPlan(model.scheduler, sampler, eta)          # an unknown name or eta outside [0, 1]: ValueError
         if plan.kind == "ddim" and plan.eta == 0:
             plan = None                                            # the step the call always had

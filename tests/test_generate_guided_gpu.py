@@ -1,4 +1,4 @@
-"""Guided / batched / v-prediction image sampling on the MI355X: the step kernel (csrc/skp_ddim_step.hip) against the fp64 formula
+"""Guided / batched / v-prediction image sampling on the MI355X: the step kernel (csrc/skp_sampler_step.hip) against the fp64 formula
 with a derived per-element bound, the image-to-bytes kernel bit for bit, and `ptp_utils.text2image_ldm_stable` with guidance, batches
 and the three prediction types against the same loop on an fp64 host copy of the modules.
 
