@@ -179,7 +179,7 @@ int skp_conv3x3_f4_gn_f32(const void* x, const void* U, const void* bias, const 
  * by the lanes on the way into the matrix cores, and the input transform runs once per launch into the workspace.
  * Shapes the kernel RUNS: Cin % 16 == 0, Cout % 64 == 0, H, W % 4 == 0 (else SKP_E_RANGE).  skp_conv3x3_f4r_ok: 1 where
  * it also PAYS against the kernels above (measured: >= 1280 channels on both sides up to 1536 tiles, <= 512 tiles with
- * >= 1920 on one; SKP_WINO_RAW=0 turns it off) -- the rule the Python layer routes by.  workspace:
+ * >= 1920 on one; the "wino_raw_max_tiles" tune key widens it) -- the rule the Python layer routes by.  workspace:
  * skp_conv3x3_f4r_workspace() bytes, REQUIRED (pre-transformed input + K-split partials).  fp32, fixed K-split order
  * (bit-reproducible). */
 int skp_conv3x3_f4r_ok(int B, int Cin, int Cout, int H, int W);

@@ -17,54 +17,84 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKP_LIB_PATH") or os.path.join(_HERE, "csrc", "libskp_hip.so")
 ABI_VERSION = 44
 
-_vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
+_i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
-# name -> argtypes   (restype is always int)
+
+class DevicePointer(C.c_void_p):
+    """A device address in an argument list.  `dtype`: the torch element type the kernel reads or writes there, None for a
+    `void*` (workspaces, streams, buffers of mixed content).  As an argtype every kind takes exactly what c_void_p takes (an
+    int, None, a c_void_p, a ctypes array or pointer): c_void_p's own conversion, already bound, with no Python frame in between."""
+    dtype = None
+    from_param = C.c_void_p.from_param
+
+
+class _vp(DevicePointer):       # void*
+    pass
+
+
+class _pf(DevicePointer):       # float*
+    dtype = torch.float32
+
+
+class _pi(DevicePointer):       # int* / int32_t*
+    dtype = torch.int32
+
+
+class _pl(DevicePointer):       # int64_t*
+    dtype = torch.int64
+
+
+class _pb(DevicePointer):       # unsigned char*
+    dtype = torch.uint8
+
+
+# [host] arrays of include/skp.h: device addresses, ints, floats (built by ptr_array / int_array / float_array)
+_hp, _hi, _hf = C.POINTER(C.c_void_p), C.POINTER(_i), C.POINTER(_f)
+
+# name -> argtypes, parameter by parameter what include/skp.h declares (tests/test_host_logic.py holds the two together);
+# restype is int, int64_t for the *_workspace entries
 SIGNATURES = {
     "skp_abi_version": [],
     "skp_tune_set": [C.c_char_p, _i],
     "skp_tune_get": [C.c_char_p],
     "skp_group_norm_onepass_ok": [_i, _i, _i, _i],
-    "skp_gemm_nt_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i,
-                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _vp],
-    "skp_qk_logits_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
-    "skp_attn_map_fwd_f32": [C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "skp_attn_map_fwd_ex_f32": [C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
-    "skp_attn_map_bwd_ex_f32": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
-                                _i, _i64, _i, _vp],
-    "skp_attn_map_bwd_workspace": [C.POINTER(_i), _i, _i, _i, _i, _i],
-    "skp_attn_map_bwd_f32": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "skp_group_norm_coef_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _f, _vp],
+    "skp_gemm_nt_f32": [_pf, _pf, _pf, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f,
+                        _vp],
+    "skp_qk_logits_f32": [_pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_attn_map_fwd_f32": [_hp, _hi, _i, _i, _i, _i, _i, _pf, _pf, _vp],
+    "skp_attn_map_fwd_ex_f32": [_hp, _hi, _i, _i, _i, _i, _i, _pf, _pf, _pf, _i, _i64, _i, _vp],
+    "skp_attn_map_bwd_ex_f32": [_hp, _hp, _hi, _i, _i, _i, _i, _i, _pf, _pf, _pf, _pf, _i, _i64, _i, _vp],
+    "skp_attn_map_bwd_workspace": [_hi, _i, _i, _i, _i, _i],
+    "skp_attn_map_bwd_f32": [_hp, _hp, _hi, _i, _i, _i, _i, _i, _pf, _pf, _pf, _vp],
+    "skp_group_norm_coef_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _pf, _i, _i, _i, _i, _f, _vp],
     "skp_conv3x3_f4_gn_ok": [_i, _i, _i, _i, _i],
-    "skp_conv3x3_f4_gn_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "skp_unwarp_accumulate_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
-    "skp_attn_map_fwd_wide_f32": [C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
-    "skp_attn_map_fwd_wide_ok": [C.POINTER(_i), _i, _i, _i],
-    "skp_attn_map_bwd_col_ok": [C.POINTER(_i), _i, _i, _i, _i, _i],
-    "skp_attn_map_bwd_col_workspace": [C.POINTER(_i), _i, _i, _i, _i, _i, _i],
-    "skp_attn_map_bwd_col_f32": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp,
-                                 _i, _vp],
-    "skp_attn_map_bwd_sparse_workspace": [C.POINTER(_i), _i, _i, _i, _i, _i, _i],
-    "skp_attn_map_bwd_sparse_f32": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp,
-                                    _i, _vp],
-    "skp_token_stats_f32": [_vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
-    "skp_select_tokens": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "skp_select_tokens_batched": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "skp_losses_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp],
-    "skp_losses_fwd_dev_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
-    "skp_rows_axpy_f32": [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp],
-    "skp_cross_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_conv3x3_f4_gn_f32": [_vp, _vp, _vp, _vp, _vp, _pf, _pf, _i, _i, _i, _i, _i, _vp],
+    "skp_unwarp_accumulate_f32": [_pf, _pf, _i, _i, _i, _i, _pf, _pf, _i, _vp],
+    "skp_attn_map_fwd_wide_f32": [_hp, _hi, _i, _i, _i, _i, _i, _pf, _pf, _pi, _i, _i, _vp],
+    "skp_attn_map_fwd_wide_ok": [_hi, _i, _i, _i],
+    "skp_attn_map_bwd_col_ok": [_hi, _i, _i, _i, _i, _i],
+    "skp_attn_map_bwd_col_workspace": [_hi, _i, _i, _i, _i, _i, _i],
+    "skp_attn_map_bwd_col_f32": [_hp, _hp, _hi, _i, _i, _i, _i, _i, _pl, _pf, _i, _pf, _vp, _i, _vp],
+    "skp_attn_map_bwd_sparse_workspace": [_hi, _i, _i, _i, _i, _i, _i],
+    "skp_attn_map_bwd_sparse_f32": [_hp, _hp, _hi, _i, _i, _i, _i, _i, _pl, _pf, _i, _pf, _vp, _i, _vp],
+    "skp_token_stats_f32": [_pf, _i, _i, _i, _f, _f, _pi, _pf, _pf, _vp],
+    "skp_select_tokens": [_pf, _pi, _i, _i, _i, _i, _pl, _pl, _vp],
+    "skp_select_tokens_batched": [_pf, _pi, _i, _i, _i, _i, _i, _pl, _pl, _vp],
+    "skp_losses_fwd_f32": [_pf, _pf, _pl, _i, _i, _i, _pi, _i, _f, _hf, _pf, _pf, _pf, _pf, _vp],
+    "skp_losses_fwd_dev_f32": [_pf, _pf, _pl, _i, _i, _i, _pi, _i, _f, _pf, _pf, _pf, _pf, _pf, _vp],
+    "skp_rows_axpy_f32": [_pf, _pl, _i, _i64, _pf, _pf, _pf, _pf, _vp],
+    "skp_cross_attn_fwd_f32": [_pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _vp],
     "skp_cross_attn_bwd_workspace": [_i, _i, _i, _i, _i],
-    "skp_cross_attn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_cross_attn_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _vp],
     "skp_text_attn_fwd_ok": [_i, _i, _i, _i, _i],
-    "skp_text_attn_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
-    "skp_group_norm_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "skp_group_norm_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "skp_group_norm_bwd_add_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "skp_add_bias_residual_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "skp_text_attn_fwd_f32": [_pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_group_norm_fwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_group_norm_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_group_norm_bwd_add_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_add_bias_residual_f32": [_pf, _pf, _pf, _pf, _i, _i, _i, _vp],
     "skp_add_layer_norm_ok": [_i],
-    "skp_add_layer_norm_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp],
-    "skp_add_layer_norm_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
+    "skp_add_layer_norm_fwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _i64, _i, _f, _vp],
+    "skp_add_layer_norm_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _i64, _i, _vp],
     "skp_conv3x3_filter_f32": [_vp, _vp, _i, _i, _i, _vp],
     "skp_conv3x3_workspace": [_i, _i, _i, _i, _i, _i],
     "skp_conv3x3_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -73,14 +103,14 @@ SIGNATURES = {
     "skp_conv3x3_f4_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "skp_flash_attn_fwd_split_ok": [_i, _i, _i, _i, _i, _i],
     "skp_flash_attn_fwd_split_workspace": [_i, _i, _i, _i, _i, _i],
-    "skp_flash_attn_fwd_split_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_float, _vp],
+    "skp_flash_attn_fwd_split_f32": [_pf, _pf, _pf, _pf, _pf, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "skp_flash_attn_fwd_wide_ok": [_i, _i, _i, _i, _i, _i],
     "skp_flash_attn_fwd_wide_workspace": [_i, _i, _i, _i, _i, _i],
-    "skp_flash_attn_fwd_wide_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_flash_attn_fwd_wide_f32": [_pf, _pf, _pf, _pf, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "skp_flash_attn_bwd_split_ok": [_i, _i, _i, _i, _i, _i],
     "skp_flash_attn_bwd_split_workspace": [_i, _i, _i, _i, _i, _i],
-    "skp_flash_attn_bwd_split_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
-    "skp_flash_attn_bwd_split_ld_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_flash_attn_bwd_split_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_flash_attn_bwd_split_ld_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     "skp_conv3x3_f4r_ok": [_i, _i, _i, _i, _i],
     "skp_conv3x3_f4r_filter_f32": [_vp, _vp, _i, _i, _i, _vp],
     "skp_conv3x3_f4r_workspace": [_i, _i, _i, _i, _i],
@@ -92,32 +122,32 @@ SIGNATURES = {
     "skp_conv3x3_s2w_ok": [_i, _i, _i, _i, _i, _i],
     "skp_conv3x3_s2w_filter_f32": [_vp, _vp, _i, _i, _i, _vp],
     "skp_conv3x3_s2w_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "skp_conv3x3_s2w_stats_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "skp_conv3x3_s2w_stats_f32": [_vp, _vp, _vp, _vp, _pf, _i, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_small_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_small_stats_blocks": [_i, _i, _i, _i, _i],
-    "skp_conv3x3_small_stats_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "skp_conv3x3_small_stats_f32": [_vp, _vp, _vp, _vp, _pf, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_up2_ok": [_i, _i, _i, _i, _i],
     "skp_conv3x3_up2_filter_f32": [_vp, _vp, _i, _i, _vp],
     "skp_conv3x3_up2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "skp_conv3x3_small_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "skp_axpby_f32": [_vp, _vp, _vp, _i64, _f, _f, _vp],
-    "skp_ddim_step_f32": [_vp, _vp, _vp, _vp, _i64, _i, _f, _i, _f, _f, _f, _f, _i, _vp],
-    "skp_sampler_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _i, _vp],
-    "skp_image_u8_nhwc_f32": [_vp, _vp, _i, _i, _i, _vp],
+    "skp_ddim_step_f32": [_pf, _pf, _pf, _pf, _i64, _i, _f, _i, _f, _f, _f, _f, _i, _vp],
+    "skp_sampler_step_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _i64, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _i, _vp],
+    "skp_image_u8_nhwc_f32": [_pf, _pb, _i, _i, _i, _vp],
     "skp_conv3x3_f4_stats_blocks": [_i, _i, _i, _i, _i],
-    "skp_conv3x3_f4_stats_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "skp_conv3x3_s2_stats_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "skp_group_norm_fwd_blocks_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
-    "skp_geglu_fwd_f32": [_vp, _vp, _i64, _i, _vp],
-    "skp_geglu_bwd_f32": [_vp, _vp, _vp, _i64, _i, _vp],
-    "skp_nchw_to_tokens_f32": [_vp, _vp, _i, _i, _i, _vp],
-    "skp_tokens_to_nchw_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "skp_flash_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_conv3x3_f4_stats_f32": [_vp, _vp, _vp, _vp, _vp, _pf, _i, _i, _i, _i, _i, _vp],
+    "skp_conv3x3_s2_stats_f32": [_vp, _vp, _vp, _vp, _pf, _i, _i, _i, _i, _i, _i, _vp],
+    "skp_group_norm_fwd_blocks_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_geglu_fwd_f32": [_pf, _pf, _i64, _i, _vp],
+    "skp_geglu_bwd_f32": [_pf, _pf, _pf, _i64, _i, _vp],
+    "skp_nchw_to_tokens_f32": [_pf, _pf, _i, _i, _i, _vp],
+    "skp_tokens_to_nchw_f32": [_pf, _pf, _pf, _i, _i, _i, _vp],
+    "skp_flash_attn_fwd_f32": [_pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _vp],
     "skp_flash_attn_bwd_workspace": [_i, _i, _i, _i, _i, _i],
-    "skp_flash_attn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
-    "skp_flash_attn_bwd_ld_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
-    "skp_self_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "skp_self_attn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "skp_flash_attn_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "skp_flash_attn_bwd_ld_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "skp_self_attn_fwd_f32": [_pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _vp],
+    "skp_self_attn_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _vp],
 }
 
 _ERR = {-1: "SKP_E_BADARG (null pointer / non-positive size)",
@@ -159,7 +189,7 @@ def lib():
 # (SKP_LAB_PATH overrides the in-checkout location, e.g. when the package is installed outside the repository tree)
 LAB_PATH = os.environ.get("SKP_LAB_PATH") or os.path.join(os.path.dirname(_HERE), "tools", "csrc", "libskp_lab.so")
 LAB_SIGNATURES = {
-    "skp_probe_mfma_f32": [_i, _i, _vp, _vp, _vp],
+    "skp_probe_mfma_f32": [_i, _i, _pf, _hf, _vp],
 }
 _lab = None
 

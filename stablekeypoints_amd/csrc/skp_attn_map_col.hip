@@ -21,8 +21,8 @@
 // K selected tokens only, no sweep), then ONE sweep launch over the natural 8-token chunks: f_t = p_t (g_t / (L H) - dot) for a
 // selected token -- its gradient row is loaded through a descriptor offset that lies past the buffer for every other token, so
 // the row code is branch-free --, f_t = -p_t dot otherwise; chunks without a selected token run the plain row code (wave-uniform
-// choice per group).  dS is written once, nothing is staged.  The two-sweep form it replaces (selected tokens first: dot + their
-// part in a side buffer, then the natural chunks) stays behind SKP_MAP_COL_DOT=0.
+// choice per group).  dS is written once, nothing is staged.  This replaced a two-sweep form (selected tokens first: dot + their
+// part in a side buffer, then the natural chunks).
 //
 // Shapes served (skp_attn_map_bwd_col_ok): R in {128, 256}, every layer R = k s with k in {4, 8} and s >= 8, T <= 1024, K <= 16
 // -- the SD-1.x path at feature_upsample_res 128 / 256; everything else keeps the other routes.

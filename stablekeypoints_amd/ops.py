@@ -33,6 +33,55 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+_ANY, _INT, _HOST = "any dtype", "an int", "a host value"      # what a slot of a launch plan takes, besides a torch dtype
+_plans = {}
+
+
+def _plan(name: str):
+    """(the entry, what each of its arguments before the stream takes) from the table of `_native`; made once per entry."""
+    slots = tuple((t.dtype or _ANY) if issubclass(t, N.DevicePointer) else _INT if t in (N._i, N._i64) else _HOST
+                  for t in N.SIGNATURES[name][:-1])
+    _plans[name] = plan = (getattr(N.lib(), name), slots)
+    return plan
+
+
+def _refused(name: str, i: int, want, a):
+    if not isinstance(a, torch.Tensor):
+        return TypeError(f"{name}: argument {i} takes an int, got {type(a).__name__} {a!r}")
+    if want in (_INT, _HOST):
+        return TypeError(f"{name}: argument {i} is no device pointer, got a tensor ({a.dtype}, {a.device})")
+    if not a.is_cuda:
+        return RuntimeError(f"{name}: argument {i}: the StableKeypoints hot path runs on the HIP kernels only "
+                            f"(got a {a.device} tensor; there is no CPU fallback)")
+    if a.get_device() != torch.cuda.current_device():
+        return RuntimeError(f"{name}: argument {i}: expected a tensor on the current device cuda:{torch.cuda.current_device()} "
+                            f"(the launch goes to its current stream), got one on {a.device}")
+    return RuntimeError(f"{name}: argument {i}: expected {want}, got {a.dtype}")
+
+
+def _launch(name: str, *args):
+    """The one way this module starts a kernel: entry `name` of include/skp.h with `args` and torch's current stream, its return
+    code checked.  A tensor stands for its address and is held to its slot first -- a device-pointer slot, on the current device,
+    of the element type the header declares (`void*` takes any) -- so a wrong tensor is an exception here, not a fault on the
+    device.  None is a null pointer; an int at a pointer slot is an address the caller has offset itself.  Nothing is copied,
+    cast or made contiguous (`_dev` does that), and strides are not looked at: column bands and batch slices pass as they are."""
+    fn, slots = _plans.get(name) or _plan(name)
+    if len(args) != len(slots):
+        raise TypeError(f"{name}: takes {len(slots)} arguments and the stream, got {len(args)}")
+    call, device = [], None
+    for a, want in zip(args, slots):
+        if isinstance(a, torch.Tensor):
+            if device is None and a.is_cuda:
+                device = torch.cuda.current_device()
+            if want is _INT or want is _HOST or a.get_device() != device or (want is not _ANY and a.dtype is not want):
+                raise _refused(name, len(call), want, a)
+            a = a.data_ptr()
+        elif want is _INT and isinstance(a, float):
+            raise _refused(name, len(call), want, a)
+        call.append(a)
+    N.check(fn(*call, _stream()), name)
+
+
 def _workspace(query: str, *args, device):
     """Scratch for the launch that follows: `query(*args)` bytes as ceil(bytes / 4) floats, None (a null pointer) for 0 bytes;
     a negative answer raises."""
@@ -40,6 +89,11 @@ def _workspace(query: str, *args, device):
     if nbytes < 0:
         N.check(nbytes, query)
     return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32) if nbytes else None
+
+
+def _gn_scratch(n: int, groups: int, device):
+    """Statistics scratch of the GroupNorm entries (include/skp.h, skp_group_norm_fwd_f32: "workspace: N*G*64*3 floats")."""
+    return torch.empty(n * groups * 64 * 3, device=device, dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -106,14 +160,12 @@ def qk_logits(q: torch.Tensor, k: torch.Tensor, heads: int, scale: float) -> tor
     if Ck != C or C % heads:
         raise RuntimeError("qk_logits: channel mismatch")
     S = torch.empty(B, heads, s2, (T + 15) // 16 * 16, device=q.device, dtype=torch.float32)
-    N.check(N.lib().skp_qk_logits_f32(q.data_ptr(), k.data_ptr(), S.data_ptr(), B, Bk, heads, T, s2,
-                                      C // heads, float(scale), _stream()), "skp_qk_logits_f32")
+    _launch("skp_qk_logits_f32", q, k, S, B, Bk, heads, T, s2, C // heads, float(scale))
     return S
 
 
 def _gemm_nt(A, B, Cout, M, Nn, K, Z0, Z1, sa, sb, sc, alpha):
-    N.check(N.lib().skp_gemm_nt_f32(A.data_ptr(), B.data_ptr(), Cout.data_ptr(), M, Nn, K, Z0, Z1,
-                                    *sa, *sb, *sc, float(alpha), _stream()), "skp_gemm_nt_f32")
+    _launch("skp_gemm_nt_f32", A, B, Cout, M, Nn, K, Z0, Z1, *sa, *sb, *sc, alpha)
 
 
 TOKEN_GROUP = 128          # most tokens one fused-map launch can hold (one softmax row per lane, in registers)
@@ -152,15 +204,12 @@ def _map_fwd(S: Sequence[torch.Tensor], sides: Sequence[int], B: int, H: int, T:
     dev = S[0].device
     L, ldt = len(S), S[0].shape[-1]
     si, _k2 = N.int_array(sides)
-    lib, st = N.lib(), _stream()
     if map_wide_supported(T, R, sides):
         routes.note("map.fwd", "map_wide")
         M = torch.empty(B, n_rows if tokrow is not None else T, R, R, device=dev, dtype=torch.float32)
         lse = torch.empty(B, L * H, R * R, device=dev, dtype=torch.float32)
         sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
-        N.check(lib.skp_attn_map_fwd_wide_f32(sp, si, L, B, H, T, R, M.data_ptr(), lse.data_ptr(),
-                                              tokrow.data_ptr() if tokrow is not None else None, int(n_rows), ldt, st),
-                "skp_attn_map_fwd_wide_f32")
+        _launch("skp_attn_map_fwd_wide_f32", sp, si, L, B, H, T, R, M, lse, tokrow, n_rows, ldt)
         return M, lse
     if tokrow is not None:
         raise RuntimeError("_map_fwd: row selection is served by the wide-token kernel only")
@@ -168,10 +217,8 @@ def _map_fwd(S: Sequence[torch.Tensor], sides: Sequence[int], B: int, H: int, T:
 
     def launch(t0, t1, mode, lse_out, lse_in):
         sp, _k1 = N.ptr_array([t.data_ptr() + 4 * t0 for t in S])
-        N.check(lib.skp_attn_map_fwd_ex_f32(sp, si, L, B, H, t1 - t0, R, M.data_ptr() + 4 * t0 * R * R,
-                                            lse_out.data_ptr() if lse_out is not None else None,
-                                            lse_in.data_ptr() if lse_in is not None else None,
-                                            ldt, T * R * R, mode, st), "skp_attn_map_fwd_ex_f32")
+        _launch("skp_attn_map_fwd_ex_f32", sp, si, L, B, H, t1 - t0, R, M.data_ptr() + 4 * t0 * R * R, lse_out, lse_in,
+                ldt, T * R * R, mode)
 
     if T <= TOKEN_GROUP:
         routes.note("map.fwd", "map_fused")
@@ -193,15 +240,13 @@ def _map_bwd(S, dS, sides, B, H, T, R, dM, lse):
     dev = dM.device
     L, ldt = len(S), S[0].shape[-1]
     si, _k3 = N.int_array(sides)
-    lib, st = N.lib(), _stream()
     ws = _workspace("skp_attn_map_bwd_workspace", si, L, B, H, T if T <= TOKEN_GROUP else GROUP_STEP, R, device=dev)
 
     def launch(t0, t1, mode, dot):
         sp, _k1 = N.ptr_array([t.data_ptr() + 4 * t0 for t in S])
         dp, _k2 = N.ptr_array([t.data_ptr() + 4 * t0 for t in dS])
-        N.check(lib.skp_attn_map_bwd_ex_f32(sp, dp, si, L, B, H, t1 - t0, R, dM.data_ptr() + 4 * t0 * R * R,
-                                            lse.data_ptr(), _ptr(ws), _ptr(dot),
-                                            ldt, T * R * R, mode, st), "skp_attn_map_bwd_ex_f32")
+        _launch("skp_attn_map_bwd_ex_f32", sp, dp, si, L, B, H, t1 - t0, R, dM.data_ptr() + 4 * t0 * R * R, lse, ws, dot,
+                ldt, T * R * R, mode)
 
     if T <= TOKEN_GROUP:
         routes.note("map.bwd", "map_dense")
@@ -263,8 +308,7 @@ def _map_bwd_sparse(S, sides, B, H, T, R, sel, G, lse):
     ws = _workspace(query, si, L, B, H, T, R, K, device=G.device)
     sp, _k1 = N.ptr_array([t.data_ptr() for t in S])
     dp, _k2 = N.ptr_array([t.data_ptr() for t in dS])
-    N.check(getattr(N.lib(), name)(sp, dp, si, L, B, H, T, R, sel.data_ptr(), G.data_ptr(), K, lse.data_ptr(), _ptr(ws), ldt,
-                                   _stream()), name)
+    _launch(name, sp, dp, si, L, B, H, T, R, sel, G, K, lse, ws, ldt)
     if ldt > (T + 15) // 16 * 16:                              # gap columns of a wider logits buffer: never read, keep finite
         for d_ in dS:
             d_[..., (T + 15) // 16 * 16:] = 0
@@ -392,10 +436,7 @@ def token_stats(M: torch.Tensor, num_subjects: int = 1, sigma: float = 2.0, eps:
     am = torch.empty(num_subjects, T, device=M.device, dtype=torch.int32)
     kl = torch.empty(T, device=M.device, dtype=torch.float32) if want_kl else None
     ent = torch.empty(T, device=M.device, dtype=torch.float32) if want_entropy else None
-    N.check(N.lib().skp_token_stats_f32(M.data_ptr(), T, R, num_subjects, float(sigma), float(eps),
-                                        am.data_ptr(), kl.data_ptr() if want_kl else None,
-                                        ent.data_ptr() if want_entropy else None, _stream()),
-            "skp_token_stats_f32")
+    _launch("skp_token_stats_f32", M, T, R, num_subjects, float(sigma), float(eps), am, kl, ent)
     return (am, kl, ent) if want_entropy else (am, kl)
 
 
@@ -409,8 +450,7 @@ def select_tokens(kl: torch.Tensor, argmax_t: torch.Tensor, R: int, n_cand: int,
     cand = torch.empty(n_cand, device=kl.device, dtype=torch.int64)
     sel = torch.empty(top_k, device=kl.device, dtype=torch.int64)
     am = argmax_t.reshape(-1)[:T].contiguous()
-    N.check(N.lib().skp_select_tokens(kl.data_ptr(), am.data_ptr(), T, R, n_cand, top_k, cand.data_ptr(),
-                                      sel.data_ptr(), _stream()), "skp_select_tokens")
+    _launch("skp_select_tokens", kl, am, T, R, n_cand, top_k, cand, sel)
     return cand, sel
 
 
@@ -440,10 +480,8 @@ class LossesFn(torch.autograd.Function):
         g_eq_a = torch.empty_like(g_sharp)
         g_eq_b = torch.empty_like(g_sharp)
         th, _keep = N.float_array(theta_inv)
-        N.check(N.lib().skp_losses_fwd_f32(M.data_ptr(), Mt.data_ptr(), sel.data_ptr(), K, T, R, argmax.data_ptr(),
-                                           int(num_subjects), float(sigma), th, partial.data_ptr(),
-                                           g_sharp.data_ptr(), g_eq_a.data_ptr(), g_eq_b.data_ptr(), _stream()),
-                "skp_losses_fwd_f32")
+        _launch("skp_losses_fwd_f32", M, Mt, sel, K, T, R, argmax, int(num_subjects), float(sigma), th, partial, g_sharp, g_eq_a,
+                g_eq_b)
         sums = partial.sum(dim=(1, 2)) / float(K * R * R)
         ctx.save_for_backward(sel, g_sharp, g_eq_a, g_eq_b)
         ctx.shape = (T, R)
@@ -460,10 +498,8 @@ class LossesFn(torch.autograd.Function):
         dM = torch.zeros(T, R, R, device=dev, dtype=torch.float32)
         dMt = torch.zeros(T, R, R, device=dev, dtype=torch.float32)
         K, n = sel.shape[0], R * R
-        N.check(N.lib().skp_rows_axpy_f32(dM.data_ptr(), sel.data_ptr(), K, n, g_sharp.data_ptr(), gs.data_ptr(),
-                                          g_eq_a.data_ptr(), ge.data_ptr(), _stream()), "skp_rows_axpy_f32")
-        N.check(N.lib().skp_rows_axpy_f32(dMt.data_ptr(), sel.data_ptr(), K, n, g_eq_b.data_ptr(), ge.data_ptr(),
-                                          None, None, _stream()), "skp_rows_axpy_f32")
+        _launch("skp_rows_axpy_f32", dM, sel, K, n, g_sharp, gs, g_eq_a, ge)
+        _launch("skp_rows_axpy_f32", dMt, sel, K, n, g_eq_b, ge, None, None)
         return dM, dMt, None, None, None, None, None
 
 
@@ -516,7 +552,6 @@ class MapLossesFn(torch.autograd.Function):
         g_eq_a, g_eq_b = torch.empty_like(g_sharp), torch.empty_like(g_sharp)
         nchunk = (R * R + 1023) // 1024
         partial = torch.empty(n, 2, K, nchunk, device=dev, dtype=torch.float32)
-        lib, st = N.lib(), _stream()
         # token statistics and the selection of ALL images in three launches (one workgroup per (image, token) / per image: the
         # per-image launches were 77 workgroups of 40 us each, twelve of them per step); per-token results are what the
         # per-image calls give, bit for bit
@@ -538,8 +573,7 @@ class MapLossesFn(torch.autograd.Function):
                 score_all = torch.arange(T, device=dev, dtype=torch.float32).repeat(n, 1)
             amt_all, _ = token_stats(flat[n * T:], num_subjects=1, sigma=sigma, want_kl=False)  # [1, n*T]
             cand_all = torch.empty(n, n_cand, device=dev, dtype=torch.int64)
-            N.check(lib.skp_select_tokens_batched(score_all.contiguous().data_ptr(), amt_all.data_ptr(), n, T, R, n_cand, K,
-                                                  cand_all.data_ptr(), sel_all.data_ptr(), st), "skp_select_tokens_batched")
+            _launch("skp_select_tokens_batched", score_all.contiguous(), amt_all, n, T, R, n_cand, K, cand_all, sel_all)
         for i in range(n):
             if batched:
                 am = am_all[i]
@@ -549,15 +583,12 @@ class MapLossesFn(torch.autograd.Function):
                 _, sel_i = select_tokens(score, am_t[0], R, n_cand, K)
                 sel_all[i].copy_(sel_i)
             if th_dev is not None:                   # inverse affines in device memory (a captured step: new numbers per replay)
-                N.check(lib.skp_losses_fwd_dev_f32(M[i].data_ptr(), M[n + i].data_ptr(), sel_all[i].data_ptr(), K, T, R,
-                                                   am.data_ptr(), ns, sigma, th_dev[i].data_ptr(), partial[i].data_ptr(),
-                                                   g_sharp[i].data_ptr(), g_eq_a[i].data_ptr(), g_eq_b[i].data_ptr(), st),
-                        "skp_losses_fwd_dev_f32")
+                _launch("skp_losses_fwd_dev_f32", M[i], M[n + i], sel_all[i], K, T, R, am, ns, sigma, th_dev[i], partial[i],
+                        g_sharp[i], g_eq_a[i], g_eq_b[i])
                 continue
             th, _keep = N.float_array(invert_affine(meta["thetas"][i]))
-            N.check(lib.skp_losses_fwd_f32(M[i].data_ptr(), M[n + i].data_ptr(), sel_all[i].data_ptr(), K, T, R,
-                                           am.data_ptr(), ns, sigma, th, partial[i].data_ptr(), g_sharp[i].data_ptr(),
-                                           g_eq_a[i].data_ptr(), g_eq_b[i].data_ptr(), st), "skp_losses_fwd_f32")
+            _launch("skp_losses_fwd_f32", M[i], M[n + i], sel_all[i], K, T, R, am, ns, sigma, th, partial[i], g_sharp[i],
+                    g_eq_a[i], g_eq_b[i])
         sums = partial.sum(dim=(0, 2, 3)) / float(K * R * R)
         ctx.save_for_backward(lse, sel_all, g_sharp, g_eq_a, g_eq_b, *qs, *ks, *S)
         ctx.meta = (R, H, scales, tuple(sides), B, T, L)
@@ -594,8 +625,7 @@ def unwarp_accumulate(maps: torch.Tensor, theta_inv: torch.Tensor, size: int, fi
     for k0 in range(0, K, UNWARP_MAX_K):
         k1 = min(K, k0 + UNWARP_MAX_K)
         chunk = maps if (k0 == 0 and k1 == K) else maps[:, k0:k1].contiguous()
-        N.check(N.lib().skp_unwarp_accumulate_f32(chunk.data_ptr(), th.data_ptr(), n, k1 - k0, R, size, tot[k0:k1].data_ptr(),
-                                                  num.data_ptr(), 1 if finish else 0, _stream()), "skp_unwarp_accumulate_f32")
+        _launch("skp_unwarp_accumulate_f32", chunk, th, n, k1 - k0, R, size, tot[k0:k1], num, 1 if finish else 0)
     return tot, num
 
 
@@ -623,9 +653,7 @@ class CrossAttnFn(torch.autograd.Function):
         out = torch.empty_like(q)
         lse = torch.empty(B, heads, Nq, device=q.device, dtype=torch.float32)
         routes.note("attn.cross", routes.cross_attn_form(B, heads, Nq, T, C // heads, N.lib().skp_tune_get(b"cross_attn_ts") == 1))
-        N.check(N.lib().skp_cross_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                               B, Bk, heads, Nq, T, C // heads, float(scale), _stream()),
-                "skp_cross_attn_fwd_f32")
+        _launch("skp_cross_attn_fwd_f32", q, k, v, out, lse, B, Bk, heads, Nq, T, C // heads, float(scale))
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.meta = (heads, float(scale))
         return out
@@ -641,10 +669,7 @@ class CrossAttnFn(torch.autograd.Function):
         dk = torch.empty(B, T, C, device=q.device, dtype=torch.float32)
         dv = torch.empty_like(dk)
         ws = _workspace("skp_cross_attn_bwd_workspace", B, heads, Nq, T, C // heads, device=q.device)
-        N.check(N.lib().skp_cross_attn_bwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _ptr(ws),
-                                               B, Bk, heads, Nq, T, C // heads, scale, _stream()),
-                "skp_cross_attn_bwd_f32")
+        _launch("skp_cross_attn_bwd_f32", q, k, v, out, dout, lse, dq, dk, dv, ws, B, Bk, heads, Nq, T, C // heads, scale)
         if Bk == 1 and B > 1:
             dk, dv = dk.sum(dim=0, keepdim=True), dv.sum(dim=0, keepdim=True)
         return dq, dk, dv, None, None
@@ -717,8 +742,7 @@ def text_attention(qkv_or_q, k, v, heads: int, scale: float):
         return _text_attn_lib(q, k, v, int(heads), float(scale))
     routes.note("text.attention", "causal_fused")
     out = torch.empty(B, Nn, C, device=q.device, dtype=torch.float32)
-    N.check(N.lib().skp_text_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, int(heads), Nn, d, ld,
-                                          float(scale), _stream()), "skp_text_attn_fwd_f32")
+    _launch("skp_text_attn_fwd_f32", q, k, v, out, B, heads, Nn, d, ld, float(scale))
     return out
 
 
@@ -745,18 +769,12 @@ class GroupNormSiLUFn(torch.autograd.Function):
         if blocks is not None:                       # statistics from the producing convolution's epilogue
             routes.note("group_norm.stats", "producer_blocks")
             bs, nblk, pix = blocks
-            N.check(N.lib().skp_group_norm_fwd_blocks_f32(x.data_ptr(), off_c.data_ptr() if off_c is not None else None,
-                                                          gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                          rstd.data_ptr(), bs.data_ptr(), int(nblk), int(pix), Nn, C, groups,
-                                                          Hh * Ww, float(eps), int(silu), _stream()),
-                    "skp_group_norm_fwd_blocks_f32")
+            _launch("skp_group_norm_fwd_blocks_f32", x, off_c, gamma, beta, y, mean, rstd, bs, nblk, pix, Nn, C, groups, Hh * Ww,
+                    float(eps), silu)
         else:
             routes.note("group_norm.stats", "own_pass")
-            ws = torch.empty(Nn * groups * 64 * 3, device=x.device, dtype=torch.float32)
-            N.check(N.lib().skp_group_norm_fwd_f32(x.data_ptr(), off_c.data_ptr() if off_c is not None else None,
-                                                   gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                   rstd.data_ptr(), ws.data_ptr(), Nn, C, groups, Hh * Ww, float(eps),
-                                                   int(silu), _stream()), "skp_group_norm_fwd_f32")
+            ws = _gn_scratch(Nn, groups, x.device)
+            _launch("skp_group_norm_fwd_f32", x, off_c, gamma, beta, y, mean, rstd, ws, Nn, C, groups, Hh * Ww, float(eps), silu)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(x, off_c if off_c is not None else x.new_empty(0), gamma, beta, mean, rstd)
         ctx.meta = (groups, float(eps), bool(silu), off_c is not None)
@@ -769,11 +787,9 @@ class GroupNormSiLUFn(torch.autograd.Function):
         dy = _dev(dy, "dy")
         Nn, C, Hh, Ww = x.shape
         dx = torch.empty_like(x)
-        ws = torch.empty(Nn * groups * 64 * 3, device=x.device, dtype=torch.float32)
-        N.check(N.lib().skp_group_norm_bwd_f32(x.data_ptr(), off_c.data_ptr() if has_off else None, gamma.data_ptr(),
-                                               beta.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                               dx.data_ptr(), ws.data_ptr(), Nn, C, groups, Hh * Ww, eps, int(silu),
-                                               _stream()), "skp_group_norm_bwd_f32")
+        ws = _gn_scratch(Nn, groups, x.device)
+        _launch("skp_group_norm_bwd_f32", x, off_c if has_off else None, gamma, beta, dy, mean, rstd, dx, ws, Nn, C, groups,
+                Hh * Ww, eps, silu)
         return dx, None, None, None, None, None, None, None
 
 
@@ -799,11 +815,9 @@ class GroupNormSiLUForkFn(torch.autograd.Function):
             return dxp, None, None, None, None, None, None, None
         dy, dxp = _dev(dy, "dy"), _dev(dxp, "dx'")
         dx = torch.empty_like(x)
-        ws = torch.empty(Nn * groups * 64 * 3, device=x.device, dtype=torch.float32)
-        N.check(N.lib().skp_group_norm_bwd_add_f32(x.data_ptr(), off_c.data_ptr() if has_off else None, gamma.data_ptr(),
-                                                   beta.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   dx.data_ptr(), dxp.data_ptr(), ws.data_ptr(), Nn, C, groups, Hh * Ww, eps,
-                                                   int(silu), _stream()), "skp_group_norm_bwd_add_f32")
+        ws = _gn_scratch(Nn, groups, x.device)
+        _launch("skp_group_norm_bwd_add_f32", x, off_c if has_off else None, gamma, beta, dy, mean, rstd, dx, dxp, ws, Nn, C,
+                groups, Hh * Ww, eps, silu)
         return dx, None, None, None, None, None, None, None
 
 
@@ -868,17 +882,15 @@ def _flash_fwd(q, k, v, out, lse, heads, scale, split=None):
     if split:
         routes.note("flash.fwd", "flash_split")
         ws = _workspace("skp_flash_attn_fwd_split_workspace", *shape, device=q.device)
-        N.check(N.lib().skp_flash_attn_fwd_split_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                                     _ptr(ws), *shape, float(scale), _stream()), "skp_flash_attn_fwd_split_f32")
+        _launch("skp_flash_attn_fwd_split_f32", q, k, v, out, lse, ws, *shape, float(scale))
     else:
         routes.note("flash.fwd", "flash_f32" if shape[5] in FA2_HEAD_DIMS else "self_attn_gen1")
-        N.check(N.lib().skp_flash_attn_fwd_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                               *shape, float(scale), _stream()), "skp_flash_attn_fwd_f32")
+        _launch("skp_flash_attn_fwd_f32", q, k, v, out, lse, *shape, float(scale))
 
 
 def _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, ld, split=None):
-    """dq, dk, dv of `_flash_fwd` into the device addresses dq / dk / dv, rows `ld` floats apart (H*d: dense tensors; dk / dv
-    hold B rows even for a shared k / v); `split` as in `_flash_fwd`."""
+    """dq, dk, dv of `_flash_fwd` into dq / dk / dv -- tensors, or the device addresses of column bands -- rows `ld` floats apart
+    (H*d: dense tensors; dk / dv hold B rows even for a shared k / v); `split` as in `_flash_fwd`."""
     B, Nq, C = q.shape
     Bk, Nk, _ = k.shape
     shape = (B, Bk, heads, Nq, Nk, C // heads)
@@ -891,15 +903,14 @@ def _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, ld, split=None
         query, name = "skp_flash_attn_bwd_workspace", "skp_flash_attn_bwd_ld_f32"
         routes.note("flash.bwd", "flash_f32" if shape[5] in FA2_HEAD_DIMS else "self_attn_gen1")
     ws = _workspace(query, *shape, device=q.device)
-    N.check(getattr(N.lib(), name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
-                                   dq, dk, dv, _ptr(ws), *shape, float(scale), int(ld), _stream()), name)
+    _launch(name, q, k, v, out, dout, lse, dq, dk, dv, ws, *shape, float(scale), ld)
 
 
 def flash_attn_bwd_split(q, k, v, out, dout, lse, heads: int, scale: float):
     """Direct entry (tests / tools): (dq, dk, dv) of the split backward (self-attention shapes)."""
     q, k, v, out, dout, lse = (_dev(t_, "t") for t_ in (q, k, v, out, dout, lse))
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.shape[2], split=True)
+    _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, q.shape[2], split=True)
     return dq, dk, dv
 
 
@@ -937,7 +948,7 @@ class FlashAttnFn(torch.autograd.Function):
         dq = torch.empty_like(q)
         dk = torch.empty(B, Nk, C, device=q.device, dtype=torch.float32)
         dv = torch.empty_like(dk)
-        _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), C)
+        _flash_bwd(q, k, v, out, dout, lse, heads, scale, dq, dk, dv, C)
         if Bk == 1 and B > 1:
             dk, dv = dk.sum(dim=0, keepdim=True), dv.sum(dim=0, keepdim=True)
         return dq, dk, dv, None, None
@@ -988,8 +999,7 @@ def flash_attn_wide(q, k, v, heads: int, scale: float):
     shape = (B, Bk, heads, Nq, Nk, C // heads)
     out = torch.empty_like(q)
     ws = _workspace("skp_flash_attn_fwd_wide_workspace", *shape, device=q.device)
-    N.check(N.lib().skp_flash_attn_fwd_wide_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(ws), *shape,
-                                                float(scale), _stream()), "skp_flash_attn_fwd_wide_f32")
+    _launch("skp_flash_attn_fwd_wide_f32", q, k, v, out, ws, *shape, float(scale))
     return out
 
 
@@ -1001,8 +1011,7 @@ class AddBiasResidualFn(torch.autograd.Function):
         a, b = _dev(a, "a"), _dev(b, "b")
         Nn, C, Hh, Ww = a.shape
         out = torch.empty_like(a)
-        N.check(N.lib().skp_add_bias_residual_f32(a.data_ptr(), b.data_ptr(), bias.data_ptr(), out.data_ptr(), Nn, C,
-                                                  Hh * Ww, _stream()), "skp_add_bias_residual_f32")
+        _launch("skp_add_bias_residual_f32", a, b, bias, out, Nn, C, Hh * Ww)
         return out
 
     @staticmethod
@@ -1044,9 +1053,7 @@ class AddLayerNormFn(torch.autograd.Function):
             x = torch.empty_like(h)
         else:
             x = h
-        N.check(N.lib().skp_add_layer_norm_fwd_f32(d.data_ptr() if d is not None else None, h.data_ptr(), weight.data_ptr(),
-                                                   bias.data_ptr(), x.data_ptr() if d is not None else None, n.data_ptr(),
-                                                   stat.data_ptr(), rows, C, float(eps), _stream()), "skp_add_layer_norm_fwd_f32")
+        _launch("skp_add_layer_norm_fwd_f32", d, h, weight, bias, x if d is not None else None, n, stat, rows, C, float(eps))
         ctx.save_for_backward(x, stat, weight)
         ctx.has_d = d is not None
         return x, n                                  # d None: x is the input itself (autograd hands back an alias)
@@ -1061,9 +1068,7 @@ class AddLayerNormFn(torch.autograd.Function):
             gn = _dev(gn, "gn")
             gx = _dev(gx, "gx") if gx is not None else None
             dx = torch.empty_like(x)
-            N.check(N.lib().skp_add_layer_norm_bwd_f32(gn.data_ptr(), gx.data_ptr() if gx is not None else None, x.data_ptr(),
-                                                       stat.data_ptr(), weight.data_ptr(), dx.data_ptr(), x.numel() // C, C,
-                                                       _stream()), "skp_add_layer_norm_bwd_f32")
+            _launch("skp_add_layer_norm_bwd_f32", gn, gx, x, stat, weight, dx, x.numel() // C, C)
         return (dx if ctx.has_d else None), dx, None, None, None
 
 
@@ -1107,11 +1112,11 @@ def _filters(weight, form, backward=False):
         name, per_pair = _FILTER_FORMS[form]
         U = torch.empty(per_pair * co * ci, device=w.device, dtype=torch.float32)
         if form in ("s2", "up2"):
-            N.check(getattr(N.lib(), name)(w.data_ptr(), U.data_ptr(), co, ci, _stream()), name)
+            _launch(name, w, U, co, ci)
         elif form == "s2w":
-            N.check(N.lib().skp_conv3x3_s2w_filter_f32(w.data_ptr(), U.data_ptr(), co, ci, 0, _stream()), name)
+            _launch(name, w, U, co, ci, 0)
         else:
-            N.check(getattr(N.lib(), name)(w.data_ptr(), U.data_ptr(), *((ci, co, 1) if backward else (co, ci, 0)), _stream()), name)
+            _launch(name, w, U, *((ci, co, 1) if backward else (co, ci, 0)))
         return U
     return cached(weight, ("filters", form, bool(backward)), (weight,), build)
 
@@ -1133,8 +1138,7 @@ def _conv3x3_raw(x, U, bias, cout, variant=0, split=True, residual=None, out=Non
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     ws = _workspace("skp_conv3x3_workspace", B, ci, cout, H, W, int(variant), device=x.device) if split else None
-    N.check(N.lib().skp_conv3x3_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
-                                    B, ci, cout, H, W, int(variant), _stream()), "skp_conv3x3_f32")
+    _launch("skp_conv3x3_f32", x, U, bias, residual, y, ws, B, ci, cout, H, W, int(variant))
     return y
 
 
@@ -1142,12 +1146,10 @@ def _conv3x3_f4_raw(x, U, bias, cout, split=True, residual=None, out=None, stats
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     if stats is not None:                            # unsplit launch that also leaves the output's block sums behind
-        N.check(N.lib().skp_conv3x3_f4_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(),
-                                                 stats.data_ptr(), B, ci, cout, H, W, _stream()), "skp_conv3x3_f4_stats_f32")
+        _launch("skp_conv3x3_f4_stats_f32", x, U, bias, residual, y, stats, B, ci, cout, H, W)
         return y
     ws = _workspace("skp_conv3x3_f4_workspace", B, ci, cout, H, W, device=x.device) if split else None
-    N.check(N.lib().skp_conv3x3_f4_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
-                                       B, ci, cout, H, W, _stream()), "skp_conv3x3_f4_f32")
+    _launch("skp_conv3x3_f4_f32", x, U, bias, residual, y, ws, B, ci, cout, H, W)
     return y
 
 
@@ -1156,8 +1158,7 @@ def _conv3x3_f4r_raw(x, R, bias, cout, residual=None, out=None):
     B, ci, H, W = x.shape
     y = out if out is not None else torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     ws = _workspace("skp_conv3x3_f4r_workspace", B, ci, cout, H, W, device=x.device)
-    N.check(N.lib().skp_conv3x3_f4r_f32(x.data_ptr(), R.data_ptr(), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ws),
-                                        B, ci, cout, H, W, _stream()), "skp_conv3x3_f4r_f32")
+    _launch("skp_conv3x3_f4r_f32", x, R, bias, residual, y, ws, B, ci, cout, H, W)
     return y
 
 
@@ -1317,7 +1318,7 @@ def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
 
 
 # GroupNorm(+offset)+SiLU folded into the consuming Winograd convolution (forward only, single output-channel group):
-# saves the norm's apply pass (one read + one write of the activation); SKP_GN_FOLD=0 for A/B runs.
+# saves the norm's apply pass (one read + one write of the activation); GN_FOLD = False for A/B runs.
 GN_FOLD = True
 
 
@@ -1355,22 +1356,17 @@ def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, re
     rstd = torch.empty_like(mean)
     coef = torch.empty(B, C, 2, device=x.device, dtype=torch.float32)
     blocks = _blocks(x)
-    lib, st = N.lib(), _stream()
     routes.note("group_norm", "gn_fold")
     routes.note("conv3x3", "wino4_c128")             # (the only form skp_conv3x3_f4_gn_ok admits)
     routes.note("group_norm.stats", "producer_blocks" if blocks is not None else "own_pass")
     if blocks is not None:
         bs, nblk, pix = blocks
-        N.check(lib.skp_group_norm_coef_f32(None, off_c.data_ptr() if off_c is not None else None, norm.weight.data_ptr(),
-                                            norm.bias.data_ptr(), mean.data_ptr(), rstd.data_ptr(), coef.data_ptr(),
-                                            bs.data_ptr(), int(nblk), int(pix), None, B, C, G, H * W, float(norm.eps), st),
-                "skp_group_norm_coef_f32")
+        _launch("skp_group_norm_coef_f32", None, off_c, norm.weight, norm.bias, mean, rstd, coef, bs, nblk, pix, None, B, C, G,
+                H * W, float(norm.eps))
     else:
-        ws = torch.empty(B * G * 64 * 3, device=x.device, dtype=torch.float32)
-        N.check(lib.skp_group_norm_coef_f32(x.data_ptr(), off_c.data_ptr() if off_c is not None else None,
-                                            norm.weight.data_ptr(), norm.bias.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            coef.data_ptr(), None, 0, 0, ws.data_ptr(), B, C, G, H * W, float(norm.eps), st),
-                "skp_group_norm_coef_f32")
+        ws = _gn_scratch(B, G, x.device)
+        _launch("skp_group_norm_coef_f32", x, off_c, norm.weight, norm.bias, mean, rstd, coef, None, 0, 0, ws, B, C, G, H * W,
+                float(norm.eps))
     U = _filters(weight, "f4")
     y = torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
     nblk = conv3x3_stats_blocks(x.shape, weight.shape) if (want_stats and _stats_useful(cout, H, W)) else 0
@@ -1378,10 +1374,8 @@ def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, re
     chunk = _rows_per_launch(C, cout, H, W)
     for b0 in range(0, B, chunk):
         b1 = min(B, b0 + chunk)
-        N.check(lib.skp_conv3x3_f4_gn_f32(x[b0:b1].data_ptr(), U.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                          residual[b0:b1].data_ptr() if residual is not None else None, y[b0:b1].data_ptr(),
-                                          stats[b0:b1].data_ptr() if stats is not None else None, coef[b0:b1].data_ptr(),
-                                          b1 - b0, C, cout, H, W, st), "skp_conv3x3_f4_gn_f32")
+        _launch("skp_conv3x3_f4_gn_f32", x[b0:b1], U, bias, residual[b0:b1] if residual is not None else None, y[b0:b1],
+                stats[b0:b1] if stats is not None else None, coef[b0:b1], b1 - b0, C, cout, H, W)
     if stats is not None:
         y._skp_blocks = (stats, nblk, 256)
     return y
@@ -1399,12 +1393,10 @@ def conv3x3_small(x, weight, bias=None, want_stats=False):
     nblk = int(N.lib().skp_conv3x3_small_stats_blocks(B, ci, w.shape[0], H, W)) if (want_stats and GN_FUSED_STATS) else 0
     if nblk:
         stats = torch.empty(B, w.shape[0], nblk, 2, device=x.device, dtype=torch.float32)
-        N.check(N.lib().skp_conv3x3_small_stats_f32(x.data_ptr(), w.data_ptr(), bb.data_ptr() if bb is not None else None, y.data_ptr(),
-                                                    stats.data_ptr(), B, ci, w.shape[0], H, W, _stream()), "skp_conv3x3_small_stats_f32")
+        _launch("skp_conv3x3_small_stats_f32", x, w, bb, y, stats, B, ci, w.shape[0], H, W)
         y._skp_blocks = (stats, nblk, 512)
         return y
-    N.check(N.lib().skp_conv3x3_small_f32(x.data_ptr(), w.data_ptr(), bb.data_ptr() if bb is not None else None, y.data_ptr(),
-                                          B, ci, w.shape[0], H, W, _stream()), "skp_conv3x3_small_f32")
+    _launch("skp_conv3x3_small_f32", x, w, bb, y, B, ci, w.shape[0], H, W)
     return y
 
 
@@ -1416,8 +1408,7 @@ def conv3x3_small_out(x, weight, bias=None, image=False):
     B, ci, H, W = x.shape
     y = torch.empty(B, w.shape[0], H, W, device=x.device, dtype=torch.float32)
     bb = _dev(bias.detach(), "bias") if bias is not None else None
-    N.check(N.lib().skp_conv3x3_small_out_f32(x.data_ptr(), w.data_ptr(), _ptr(bb), y.data_ptr(), B, ci, w.shape[0], H, W,
-                                              int(bool(image)), _stream()), "skp_conv3x3_small_out_f32")
+    _launch("skp_conv3x3_small_out_f32", x, w, bb, y, B, ci, w.shape[0], H, W, bool(image))
     return y
 
 
@@ -1478,8 +1469,7 @@ def conv3x3_up2(x, weight, bias=None):
         U = _filters(weight, "up2")
         y = torch.empty(B, co, 2 * H, 2 * W, device=x.device, dtype=torch.float32)
         bb = _dev(bias.detach(), "bias") if bias is not None else None
-        N.check(N.lib().skp_conv3x3_up2_f32(x.data_ptr(), U.data_ptr(), _ptr(bb), y.data_ptr(), B, ci, co, H, W, _stream()),
-                "skp_conv3x3_up2_f32")
+        _launch("skp_conv3x3_up2_f32", x, U, bb, y, B, ci, co, H, W)
         return y
     routes.note("upsample_conv", "interp_wino")
     return conv3x3_auto(torch.nn.functional.interpolate(x, scale_factor=2.0, mode="nearest"), weight, bias)
@@ -1491,7 +1481,7 @@ def axpby(x, z, a: float, b: float):
     if x.shape != z.shape:
         raise RuntimeError("axpby: shapes differ")
     y = torch.empty_like(x)
-    N.check(N.lib().skp_axpby_f32(x.data_ptr(), z.data_ptr(), y.data_ptr(), x.numel(), float(a), float(b), _stream()), "skp_axpby_f32")
+    _launch("skp_axpby_f32", x, z, y, x.numel(), float(a), float(b))
     return y
 
 
@@ -1527,9 +1517,8 @@ def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, g
     twice along dim 0.  `out`: a contiguous float32 tensor of copies * x.numel() elements to write into; it may be x itself, or
     (copies = 2) a buffer whose first half x is."""
     x, m_c, m_u, _, pred, n, out = _step_args("ddim_step", x, m_c, m_u, None, None, prediction, copies, out)
-    N.check(N.lib().skp_ddim_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), out.data_ptr(), n, int(copies), float(guidance),
-                                      pred, float(sa), float(sb), float(pa), float(pb), int(bool(clip)), _stream()),
-            "skp_ddim_step_f32")
+    _launch("skp_ddim_step_f32", x, m_c, m_u, out, n, copies, float(guidance), pred, float(sa), float(sb), float(pa), float(pb),
+            bool(clip))
     return out
 
 
@@ -1548,9 +1537,8 @@ def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: 
     if x0_out is not None and not (x0_out.is_cuda and x0_out.dtype == torch.float32 and x0_out.is_contiguous()
                                    and x0_out.numel() == n):
         raise RuntimeError("sampler_step: `x0_out` must be a contiguous float32 device tensor of x.numel() elements")
-    N.check(N.lib().skp_sampler_step_f32(x.data_ptr(), m_c.data_ptr(), _ptr(m_u), _ptr(x0_prev), _ptr(noise), out.data_ptr(),
-                                         _ptr(x0_out), n, int(copies), float(guidance), pred, sa, sb, cx, c0, ce, c1, cn,
-                                         int(bool(clip)), _stream()), "skp_sampler_step_f32")
+    _launch("skp_sampler_step_f32", x, m_c, m_u, x0_prev, noise, out, x0_out, n, copies, float(guidance), pred, sa, sb, cx, c0, ce,
+            c1, cn, bool(clip))
     return out
 
 
@@ -1562,7 +1550,7 @@ def image_u8_nhwc(x):
         raise RuntimeError(f"image_u8_nhwc: expected [B,3,H,W], got {tuple(x.shape)}")
     B, _, H, W = x.shape
     y = torch.empty(B, H, W, 3, device=x.device, dtype=torch.uint8)
-    N.check(N.lib().skp_image_u8_nhwc_f32(x.data_ptr(), y.data_ptr(), B, H, W, _stream()), "skp_image_u8_nhwc_f32")
+    _launch("skp_image_u8_nhwc_f32", x, y, B, H, W)
     return y
 
 
@@ -1573,7 +1561,7 @@ def mfma_issue_rate(waves_per_simd: int = 1, iters: int = 20000, device=None) ->
     scratch = torch.empty(256 * 4 * 256, device=dev, dtype=torch.float32)
     out = ctypes.c_float(0.0)
     with torch.cuda.device(dev):
-        N.check(N.lab().skp_probe_mfma_f32(int(waves_per_simd), int(iters), scratch.data_ptr(), ctypes.addressof(out), _stream()),
+        N.check(N.lab().skp_probe_mfma_f32(int(waves_per_simd), int(iters), scratch.data_ptr(), ctypes.byref(out), _stream()),
                 "skp_probe_mfma_f32")
     return float(out.value)
 
@@ -1776,25 +1764,21 @@ def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
         nblk = (H // 8) * (W // 8) // 16
         if want_stats and GN_FUSED_STATS and nblk * 16 == (H // 8) * (W // 8):
             stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
-            N.check(N.lib().skp_conv3x3_s2w_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), stats.data_ptr(),
-                                                      B, ci, co, H, W, int(pad), _stream()), "skp_conv3x3_s2w_stats_f32")
+            _launch("skp_conv3x3_s2w_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))
             y._skp_blocks = (stats, nblk, 256)
             return y
-        N.check(N.lib().skp_conv3x3_s2w_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), B, ci, co, H, W, int(pad),
-                                            _stream()), "skp_conv3x3_s2w_f32")
+        _launch("skp_conv3x3_s2w_f32", x, U, bias, y, B, ci, co, H, W, int(pad))
         return y
     routes.note("conv3x3_s2", "s2_direct")
     U = _filters(weight, "s2")
     if want_stats and GN_FUSED_STATS:
         nblk = (H // 16) * (W // 32)
         stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
-        N.check(N.lib().skp_conv3x3_s2_stats_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), stats.data_ptr(),
-                                                 B, ci, co, H, W, int(pad), _stream()), "skp_conv3x3_s2_stats_f32")
+        _launch("skp_conv3x3_s2_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))
         y._skp_blocks = (stats, nblk, 128)
         return y
     ws = _workspace("skp_conv3x3_s2_workspace", B, ci, co, H, W, device=x.device)    # small grid: K split over the input channels
-    N.check(N.lib().skp_conv3x3_s2_ws_f32(x.data_ptr(), U.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(ws), B, ci, co, H, W,
-                                          int(pad), _stream()), "skp_conv3x3_s2_ws_f32")
+    _launch("skp_conv3x3_s2_ws_f32", x, U, bias, y, ws, B, ci, co, H, W, int(pad))
     return y
 
 
@@ -1807,7 +1791,7 @@ class GEGLUFn(torch.autograd.Function):
         inner = proj.shape[-1] // 2
         rows = proj.numel() // (2 * inner)
         y = torch.empty(*proj.shape[:-1], inner, device=proj.device, dtype=torch.float32)
-        N.check(N.lib().skp_geglu_fwd_f32(proj.data_ptr(), y.data_ptr(), rows, inner, _stream()), "skp_geglu_fwd_f32")
+        _launch("skp_geglu_fwd_f32", proj, y, rows, inner)
         ctx.save_for_backward(proj)
         return y
 
@@ -1817,8 +1801,7 @@ class GEGLUFn(torch.autograd.Function):
         dy = _dev(dy, "dy")
         inner = proj.shape[-1] // 2
         dp = torch.empty_like(proj)
-        N.check(N.lib().skp_geglu_bwd_f32(proj.data_ptr(), dy.data_ptr(), dp.data_ptr(), proj.numel() // (2 * inner), inner,
-                                          _stream()), "skp_geglu_bwd_f32")
+        _launch("skp_geglu_bwd_f32", proj, dy, dp, proj.numel() // (2 * inner), inner)
         return dp
 
 
@@ -1829,15 +1812,14 @@ def geglu(proj):
 def _to_tokens_raw(x):
     B, C, H, W = x.shape
     y = torch.empty(B, H * W, C, device=x.device, dtype=torch.float32)
-    N.check(N.lib().skp_nchw_to_tokens_f32(x.data_ptr(), y.data_ptr(), B, C, H * W, _stream()), "skp_nchw_to_tokens_f32")
+    _launch("skp_nchw_to_tokens_f32", x, y, B, C, H * W)
     return y
 
 
 def _to_nchw_raw(t, res, H, W):
     B, HW, C = t.shape
     y = torch.empty(B, C, H, W, device=t.device, dtype=torch.float32)
-    N.check(N.lib().skp_tokens_to_nchw_f32(t.data_ptr(), res.data_ptr() if res is not None else None, y.data_ptr(), B, C,
-                                           HW, _stream()), "skp_tokens_to_nchw_f32")
+    _launch("skp_tokens_to_nchw_f32", t, res, y, B, C, HW)
     return y
 
 

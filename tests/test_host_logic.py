@@ -25,6 +25,146 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.skp_token_stats_f32(None, 0, 0, 1, 1.0, 1e-5, None, None, None, None) == -1
 
 
+_C_SCALARS = {"int": "int", "int64_t": "int64", "float": "float"}
+_C_ELEMENTS = {"float": "f32", "int": "i32", "int32_t": "i32", "int64_t": "i64", "unsigned char": "u8", "void": "void"}
+
+
+def _header_abi(text):
+    """{entry: (return type, [parameter kind, ...])} of a C header in the style of include/skp.h.  Kinds: "int" | "int64" |
+    "float" | "char*" | "dev:f32|i32|i64|u8|void" (a device pointer by element type) | "host:ptr|int|float" (a parameter whose
+    comment starts with [host]: an array in host memory of device addresses, ints or floats)."""
+    text = re.sub(r"/\*\s*\[host\].*?\*/", " HOSTMARK ", text, flags=re.S)
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    abi = {}
+    for ret, name, params in re.findall(r"^(int|int64_t)\s+(skp_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        kinds = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            host = "HOSTMARK" in p
+            words = re.sub(r"\bconst\b|HOSTMARK", " ", p).replace("*", " * ").split()
+            assert len(words) >= 2 and re.fullmatch(r"\w+", words[-1]), f"{name}: cannot read parameter {p!r}"
+            base, stars = " ".join(w for w in words[:-1] if w != "*"), words[:-1].count("*")
+            if host:
+                assert stars in (1, 2) and (stars == 2 or base in ("int", "float")), f"{name}: unknown host array {p!r}"
+                kinds.append("host:ptr" if stars == 2 else "host:" + base)
+            elif stars == 0:
+                kinds.append(_C_SCALARS[base])
+            else:
+                assert stars == 1, f"{name}: pointer to pointer without [host]: {p!r}"
+                kinds.append("char*" if base == "char" else "dev:" + _C_ELEMENTS[base])
+        assert name not in abi, f"{name} declared twice"
+        abi[name] = (ret, kinds)
+    return abi
+
+
+def _table_kind(t):
+    """The same kind names for an argtype of _native.SIGNATURES."""
+    import ctypes as C
+    from stablekeypoints_amd import _native as N
+    if isinstance(t, type) and issubclass(t, N.DevicePointer):
+        return "dev:" + {None: "void", torch.float32: "f32", torch.int32: "i32", torch.int64: "i64", torch.uint8: "u8"}[t.dtype]
+    return {C.c_int: "int", C.c_int64: "int64", C.c_float: "float", C.c_char_p: "char*", C.POINTER(C.c_void_p): "host:ptr",
+            C.POINTER(C.c_int): "host:int", C.POINTER(C.c_float): "host:float"}.get(t, f"unknown:{t!r}")
+
+
+def _abi_mismatches(header_text, table):
+    """Every disagreement between a header and a table of argtypes, one line each (an empty list: they agree)."""
+    abi, out = _header_abi(header_text), []
+    for name in sorted(set(abi) | set(table)):
+        if name not in abi or name not in table:
+            out.append(f"{name}: only in the {'table' if name in table else 'header'}")
+            continue
+        ret, want = abi[name]
+        got = [_table_kind(t) for t in table[name]]
+        if (ret == "int64_t") != name.endswith("_workspace"):
+            out.append(f"{name}: returns {ret} (the binding takes int64_t for the *_workspace entries only)")
+        if len(got) != len(want):
+            out.append(f"{name}: {len(want)} parameters in the header, {len(got)} in the table")
+        out += [f"{name}: parameter {i}: header {w}, table {g}" for i, (w, g) in enumerate(zip(want, got)) if w != g]
+    return out
+
+
+def test_ctypes_tables_agree_with_the_headers_type_by_type():
+    """SIGNATURES against include/skp.h and LAB_SIGNATURES against tools/csrc/skp_lab.h, parameter by parameter: scalar kinds, host
+    arrays and their element types, the element type of every device pointer, char*, the return-type rule, parameter counts."""
+    from stablekeypoints_amd import _native as N
+    hdr = open(os.path.join(ROOT, "include", "skp.h")).read()
+    abi = _header_abi(hdr)
+    assert len(abi) == len(N.SIGNATURES) == len(set(re.findall(r"^int(?:64_t)?\s+(skp_\w+)\s*\(", hdr, flags=re.M))) >= 93
+    assert _abi_mismatches(hdr, N.SIGNATURES) == []
+    kinds = [k for _, ks in abi.values() for k in ks]
+    assert {k: kinds.count(k) for k in sorted(set(kinds)) if k.startswith(("dev:", "host:", "char"))} == {
+        "char*": 2, "dev:f32": 226, "dev:i32": 6, "dev:i64": 9, "dev:u8": 1, "dev:void": 150,
+        "host:float": 1, "host:int": 12, "host:ptr": 11}
+    for name, (_, ks) in abi.items():               # what ops._launch relies on: a launching entry ends in the stream
+        if not name.endswith(("_ok", "_workspace", "_stats_blocks", "_version", "_tune_set", "_tune_get")):
+            assert ks[-1] == "dev:void", name
+    assert _abi_mismatches(open(os.path.join(ROOT, "tools", "csrc", "skp_lab.h")).read(), N.LAB_SIGNATURES) == []
+
+
+def test_abi_comparison_reports_a_wrong_table():
+    """The comparison above can fail: one perturbed entry at a time in a COPY of the table, each reported by name and position."""
+    from stablekeypoints_amd import _native as N
+    hdr = open(os.path.join(ROOT, "include", "skp.h")).read()
+
+    def perturbed(name, edit):
+        table = {k: list(v) for k, v in N.SIGNATURES.items()}
+        edit(table[name])
+        return _abi_mismatches(hdr, table)
+
+    def narrow_rows(a):
+        assert a[2] is N._i64
+        a[2] = N._i
+
+    def retype_x(a):
+        assert a[0] is N._pf
+        a[0] = N._pl
+
+    assert perturbed("skp_geglu_fwd_f32", narrow_rows) == ["skp_geglu_fwd_f32: parameter 2: header int64, table int"]
+    assert perturbed("skp_ddim_step_f32", retype_x) == ["skp_ddim_step_f32: parameter 0: header dev:f32, table dev:i64"]
+    assert perturbed("skp_axpby_f32", list.pop) == ["skp_axpby_f32: 7 parameters in the header, 6 in the table"]
+    assert perturbed("skp_attn_map_fwd_f32", lambda a: a.__setitem__(1, N._pi)) == [
+        "skp_attn_map_fwd_f32: parameter 1: header host:int, table dev:i32"]
+    table = dict(N.SIGNATURES)
+    del table["skp_axpby_f32"]
+    assert _abi_mismatches(hdr, table) == ["skp_axpby_f32: only in the header"]
+    assert N.SIGNATURES["skp_geglu_fwd_f32"][2] is N._i64 and "skp_axpby_f32" in N.SIGNATURES     # the live table is untouched
+
+
+def test_launch_refuses_wrong_arguments_before_entering_the_library(monkeypatch):
+    """ops._launch holds an argument list to the entry's table row before anything is launched: each refusal below names the
+    entry, and the entry itself is never called (it is replaced by one that fails the test)."""
+    from stablekeypoints_amd import ops
+
+    def entered(*a):
+        raise AssertionError("the library was entered")
+
+    name = "skp_axpby_f32"                           # (x, z, y, int64 n, float a, float b, stream)
+    monkeypatch.setitem(ops._plans, name, (entered, ops._plan(name)[1]))
+    x, y = torch.zeros(8), torch.zeros(8)
+    with pytest.raises(RuntimeError, match=rf"{name}: argument 1: .*no CPU fallback"):
+        ops._launch(name, None, x, None, 8, 1.0, 1.0)
+    with pytest.raises(TypeError, match=rf"{name}: takes 6 arguments and the stream, got 7"):
+        ops._launch(name, None, None, None, 8, 1.0, 1.0, 0)
+    with pytest.raises(TypeError, match=rf"{name}: takes 6 arguments and the stream, got 5"):
+        ops._launch(name, None, None, None, 8, 1.0)
+    with pytest.raises(TypeError, match=rf"{name}: argument 3 is no device pointer, got a tensor"):
+        ops._launch(name, None, None, None, torch.tensor(8), 1.0, 1.0)
+    with pytest.raises(TypeError, match=rf"{name}: argument 4 is no device pointer, got a tensor"):
+        ops._launch(name, None, None, None, 8, y, 1.0)
+    with pytest.raises(TypeError, match=rf"{name}: argument 3 takes an int, got float 8.0"):
+        ops._launch(name, None, None, None, 8.0, 1.0, 1.0)
+    with pytest.raises(RuntimeError, match="skp_select_tokens: argument 0: .*no CPU fallback"):
+        monkeypatch.setitem(ops._plans, "skp_select_tokens", (entered, ops._plan("skp_select_tokens")[1]))
+        ops.select_tokens(torch.zeros(16), torch.zeros(16, dtype=torch.int32), 8, 4, 2)
+    # every launching entry has a plan: tensors at device-pointer slots only, one slot per parameter before the stream
+    from stablekeypoints_amd import _native as N
+    for entry, argtypes in N.SIGNATURES.items():
+        if argtypes and argtypes[-1] is N._vp:
+            slots = ops._plan(entry)[1]
+            assert len(slots) == len(argtypes) - 1
+            assert all((s in (ops._INT, ops._HOST)) != issubclass(t, N.DevicePointer) for s, t in zip(slots, argtypes)), entry
+
+
 def test_library_reads_no_environment_and_tune_overrides_are_explicit():
     """Launch plans are functions of the shapes only: no getenv() in the library; the developer overrides go through
     skp_tune_set (tests / tools) and the package keeps to the documented switches (SKP_LIB_PATH, SKP_LAB_PATH, SKP_DIST_BACKEND,

@@ -10,7 +10,7 @@ extern "C" {
 
 /* Measurement aid (bench.py): sustained rate, in TFLOP/s, of back-to-back independent v_mfma_f32_16x16x4_f32 with
  * `waves_per_simd` (1..4) resident waves on every SIMD.  Synchronises `stream`.  scratch: >= 256*4*256 floats. */
-int skp_probe_mfma_f32(int waves_per_simd, int iters, float* scratch, float* tflops, void* stream);
+int skp_probe_mfma_f32(int waves_per_simd, int iters, float* scratch, float* tflops /*[host] 1*/, void* stream);
 
 #ifdef __cplusplus
 }
