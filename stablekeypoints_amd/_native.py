@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: libskp_hip.so has 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKP_LIB_PATH: another BUILD of the same library (same-box A/B of two kernel versions, tools/ab_build.py); never a fallback
 LIB_PATH = os.environ.get("SKP_LIB_PATH") or os.path.join(_HERE, "csrc", "libskp_hip.so")
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
@@ -150,6 +150,19 @@ SIGNATURES = {
     "skp_self_attn_bwd_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _i, _i, _i, _i, _f, _vp],
 }
 
+# include/skp_keypoints.h, held to it the same way (tests/test_keypoint_guidance_host.py); bound and launched like the entries above
+KEYPOINT_SIGNATURES = {
+    "skp_point_loss_f32": [_pf, _pf, _i, _i, _i, _f, _pf, _pf, _vp],
+    "skp_sampler_step_kp_f32": [_pf, _pf, _pf, _pf, _pf, _pf, _pf, _i64, _i, _f, _i, _f, _f, _f, _f, _f, _f, _f, _i, _pf, _pf, _i,
+                                _vp],
+}
+
+
+def signature(name):
+    """argtypes of an entry of either header."""
+    return SIGNATURES[name] if name in SIGNATURES else KEYPOINT_SIGNATURES[name]
+
+
 _ERR = {-1: "SKP_E_BADARG (null pointer / non-positive size)",
         -2: "SKP_E_RANGE (size outside the built kernel range)",
         -3: "SKP_E_LDS (tile exceeds 160 KiB LDS)"}
@@ -171,7 +184,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C stablekeypoints_amd/csrc`). There is no CPU/eager fallback for the hot path.")
     l = C.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in (*SIGNATURES.items(), *KEYPOINT_SIGNATURES.items()):
         if not hasattr(l, name):
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(l, name)

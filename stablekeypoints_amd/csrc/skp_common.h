@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/skp.h"
+#include "../../include/skp_keypoints.h"
 
 #define SKP_WAVE 64
 #define SKP_LOG2E 1.4426950408889634f

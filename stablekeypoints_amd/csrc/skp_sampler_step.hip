@@ -3,7 +3,9 @@
 //                           the eta = 0 DDIM update y = pa x0 + pb eps (ldm/scheduler.py `DDIMScheduler.step`);
 //   skp_sampler_step_f32    the same up to the clamp, then y = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise for the samplers of
 //                           ldm/samplers.py (stochastic DDIM, DPM-Solver++(2M), SDE-DPM-Solver++(2M)); the clamped x0 is kept for
-//                           the next step's x0_prev.
+//                           the next step's x0_prev;
+//   skp_sampler_step_kp_f32 the sampler form with the gradient term of keypoint guidance: between deriving (x0, eps) and the clamp,
+//                           eps += s g and x0 -= (sb / sa) s g, s = gs[row of the element] read from device memory.
 // Either may write y twice (the duplicated UNet input of the next guided step, so the loop needs no concatenation).
 // Memory-bound and tiny (a latent is 16 K floats): 16-byte accesses where pointers and counts allow, a scalar form otherwise, the grid
 // capped at 2048 workgroups with a grid-stride loop.  Every output element is computed by the lane that read its inputs, after
@@ -15,25 +17,32 @@ namespace {
 
 struct StepCoef {
     float g, sa, sb, cx, c0, ce, c1, cn;                            // cx, c1, cn: FULL only
+    float kr;                                                       // sb / sa (KP only)
     int prediction, clip;
 };
 
-// What only the FULL (sampler) form takes, each may be null; the DDIM form carries no such arguments.
+// What only the FULL (sampler) form takes, each may be null; the DDIM form carries no such arguments.  kg / kgs / per: the guidance
+// gradient, its per-row scales and the elements per row (KP only).
 template <bool FULL>
 struct StepExtra {
     const float *x0_prev, *noise;
     float* x0_out;
+    const float *kg, *kgs;
+    long long per;
 };
 template <>
 struct StepExtra<false> {
     static constexpr const float *x0_prev = nullptr, *noise = nullptr;
     static constexpr float* x0_out = nullptr;
+    static constexpr const float *kg = nullptr, *kgs = nullptr;
+    static constexpr long long per = 1;
 };
 
 // -> y; x0 (after the clamp) through `x0c`.  `p` / `nz` are 0 where x0_prev / noise are absent (their coefficients are 0 then).
 // The DDIM form is an expression of its own, not the five terms with zeros: the two contract into different fused multiply-adds.
-template <bool GUIDED, bool FULL>
-__device__ __forceinline__ float step_one(float x, float mc, float mu, float p, float nz, const StepCoef& c, float& x0c) {
+// KP: `sg` = s g of this element, the shift of eps; x0 moves by -(sb / sa) of it, so that sa x0 + sb eps stays x.
+template <bool GUIDED, bool FULL, bool KP = false>
+__device__ __forceinline__ float step_one(float x, float mc, float mu, float p, float nz, const StepCoef& c, float& x0c, float sg = 0.f) {
     const float m = GUIDED ? mu + c.g * (mc - mu) : mc;
     float x0, eps;
     if (c.prediction == 0) {
@@ -46,6 +55,10 @@ __device__ __forceinline__ float step_one(float x, float mc, float mu, float p, 
         x0 = m;
         eps = (x - c.sa * m) / c.sb;
     }
+    if (KP) {
+        eps += sg;
+        x0 -= c.kr * sg;
+    }
     if (c.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     x0c = x0;
     if (FULL) return c.cx * x + c.c0 * x0 + c.ce * eps + c.c1 * p + c.cn * nz;
@@ -55,7 +68,7 @@ __device__ __forceinline__ float step_one(float x, float mc, float mu, float p, 
 // VEC: every pointer given is 16-byte aligned; groups of four elements per lane, the n % 4 tail by the first lanes of workgroup 0.
 // Y2VEC: the second copy y + n is 16-byte aligned too (n % 4 == 0); otherwise it is written with scalar stores.
 // x / y and x0_prev / x0_out carry no __restrict__: each pair may be one buffer.
-template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL>
+template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL, bool KP = false>
 __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const float* x, const float* __restrict__ mc,
                                                                         const float* __restrict__ mu, StepExtra<FULL> e, float* y,
                                                                         long long n, int copies, StepCoef c) {
@@ -65,6 +78,8 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
     const float* x0_prev = e.x0_prev;
     const float* __restrict__ noise = e.noise;
     float* x0_out = e.x0_out;
+    const float* __restrict__ kg = e.kg;
+    const float* __restrict__ kgs = e.kgs;
     if (VEC) {
         const long long n4 = n >> 2;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -74,11 +89,24 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
             const f32x4 uv = GUIDED ? ((const f32x4*)mu)[i] : cv;
             const f32x4 pv = x0_prev ? ((const f32x4*)x0_prev)[i] : zero;
             const f32x4 nv = noise ? ((const f32x4*)noise)[i] : zero;
+            const f32x4 gv = KP ? ((const f32x4*)kg)[i] : zero;
             f32x4 r, z;
+            // the row of the group's first element, by one division; later elements step over a row's end (several, if rows are
+            // shorter than a group) and reload the scale only there
+            long long row = KP ? (4 * i) / e.per : 0;
+            long long at = KP ? 4 * i - row * e.per : 0;
+            float s = KP ? kgs[row] : 0.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float x0c;
-                r[k] = step_one<GUIDED, FULL>(xv[k], cv[k], uv[k], pv[k], nv[k], c, x0c);
+                if (KP) {
+                    while (at >= e.per) {
+                        at -= e.per;
+                        s = kgs[++row];
+                    }
+                    ++at;
+                }
+                r[k] = step_one<GUIDED, FULL, KP>(xv[k], cv[k], uv[k], pv[k], nv[k], c, x0c, s * gv[k]);
                 z[k] = x0c;
             }
             ((f32x4*)y)[i] = r;
@@ -95,8 +123,8 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
         const long long t = (n4 << 2) + tid;                        // tail: at most three elements
         if (tid < 4 && t < n) {
             float x0c;
-            const float r = step_one<GUIDED, FULL>(x[t], mc[t], GUIDED ? mu[t] : 0.f, x0_prev ? x0_prev[t] : 0.f,
-                                                   noise ? noise[t] : 0.f, c, x0c);
+            const float r = step_one<GUIDED, FULL, KP>(x[t], mc[t], GUIDED ? mu[t] : 0.f, x0_prev ? x0_prev[t] : 0.f,
+                                                       noise ? noise[t] : 0.f, c, x0c, KP ? kgs[t / e.per] * kg[t] : 0.f);
             y[t] = r;
             if (y2) y2[t] = r;
             if (x0_out) x0_out[t] = x0c;
@@ -104,8 +132,8 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
     } else {
         for (long long i = tid; i < n; i += stride) {
             float x0c;
-            const float r = step_one<GUIDED, FULL>(x[i], mc[i], GUIDED ? mu[i] : 0.f, x0_prev ? x0_prev[i] : 0.f,
-                                                   noise ? noise[i] : 0.f, c, x0c);
+            const float r = step_one<GUIDED, FULL, KP>(x[i], mc[i], GUIDED ? mu[i] : 0.f, x0_prev ? x0_prev[i] : 0.f,
+                                                       noise ? noise[i] : 0.f, c, x0c, KP ? kgs[i / e.per] * kg[i] : 0.f);
             y[i] = r;
             if (y2) y2[i] = r;
             if (x0_out) x0_out[i] = x0c;
@@ -114,21 +142,25 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
 }
 
 // The alignment decision, the grid and the launch for both entries, which have checked their arguments.  `full`: the sampler form;
-// otherwise x0_prev, noise and x0_out are null and the kernel does not take them.
+// otherwise x0_prev, noise and x0_out are null and the kernel does not take them.  `kg` (sampler form only): the guidance gradient,
+// with its `rows` scales `kgs`; null for the two entries without it.
 int step_launch(bool full, const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise, float* y,
-                float* x0_out, int64_t n, int copies, const StepCoef& c, void* stream) {
+                float* x0_out, int64_t n, int copies, const StepCoef& c, void* stream, const float* kg = nullptr,
+                const float* kgs = nullptr, int rows = 1) {
     const bool vec = skp_aligned16(x) && skp_aligned16(m_c) && skp_aligned16(m_u) && skp_aligned16(x0_prev) && skp_aligned16(noise) &&
-                     skp_aligned16(y) && skp_aligned16(x0_out) && n >= 4;
+                     skp_aligned16(y) && skp_aligned16(x0_out) && skp_aligned16(kg) && n >= 4;
+    const long long per = n / rows;
     const bool y2vec = (n & 3) == 0;
     const dim3 grid(skp_capped_grid(vec ? n / 4 : n)), block(SKP_EW_BLOCK);
     hipStream_t st = (hipStream_t)stream;
-#define SKP_STEP_AS(G, V, Y2, FULL, ...)                                                                                       \
-    hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2, FULL>), grid, block, 0, st, x, m_c, m_u, StepExtra<FULL>{__VA_ARGS__}, y, \
+#define SKP_STEP_AS(G, V, Y2, FULL, KP, ...)                                                                                           \
+    hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2, FULL, KP>), grid, block, 0, st, x, m_c, m_u, StepExtra<FULL>{__VA_ARGS__}, y, \
                        (long long)n, copies, c)
-#define SKP_STEP(G, V, Y2)                                             \
-    do {                                                               \
-        if (full) SKP_STEP_AS(G, V, Y2, true, x0_prev, noise, x0_out); \
-        else SKP_STEP_AS(G, V, Y2, false);                             \
+#define SKP_STEP(G, V, Y2)                                                                      \
+    do {                                                                                        \
+        if (kg) SKP_STEP_AS(G, V, Y2, true, true, x0_prev, noise, x0_out, kg, kgs, per);        \
+        else if (full) SKP_STEP_AS(G, V, Y2, true, false, x0_prev, noise, x0_out, nullptr, nullptr, 1); \
+        else SKP_STEP_AS(G, V, Y2, false, false);                                               \
     } while (0)
     if (m_u) {
         if (!vec) SKP_STEP(true, false, false);
@@ -155,7 +187,7 @@ __global__ __launch_bounds__(256) void skp_axpby_kernel(const float* __restrict_
 extern "C" int skp_ddim_step_f32(const float* x, const float* m_c, const float* m_u, float* y, int64_t n, int copies, float guidance,
                                  int prediction, float sa, float sb, float pa, float pb, int clip, void* stream) {
     if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
-    const StepCoef c{guidance, sa, sb, 0.f, pa, pb, 0.f, 0.f, prediction, clip ? 1 : 0};
+    const StepCoef c{guidance, sa, sb, 0.f, pa, pb, 0.f, 0.f, 0.f, prediction, clip ? 1 : 0};
     return step_launch(false, x, m_c, m_u, nullptr, nullptr, y, nullptr, n, copies, c, stream);
 }
 
@@ -166,8 +198,21 @@ extern "C" int skp_sampler_step_f32(const float* x, const float* m_c, const floa
     if ((c1 != 0.f && !x0_prev) || (cn != 0.f && !noise)) return SKP_E_BADARG;
     if (c1 == 0.f) x0_prev = nullptr;                               // not read: a buffer that holds no x0 yet may be anything, NaN included
     if (cn == 0.f) noise = nullptr;
-    const StepCoef c{guidance, sa, sb, cx, c0, ce, c1, cn, prediction, clip ? 1 : 0};
+    const StepCoef c{guidance, sa, sb, cx, c0, ce, c1, cn, 0.f, prediction, clip ? 1 : 0};
     return step_launch(true, x, m_c, m_u, x0_prev, noise, y, x0_out, n, copies, c, stream);
+}
+
+extern "C" int skp_sampler_step_kp_f32(const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise,
+                                       float* y, float* x0_out, int64_t n, int copies, float guidance, int prediction, float sa,
+                                       float sb, float cx, float c0, float ce, float c1, float cn, int clip, const float* g,
+                                       const float* gs, int rows, void* stream) {
+    if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
+    if ((c1 != 0.f && !x0_prev) || (cn != 0.f && !noise)) return SKP_E_BADARG;
+    if (!g || !gs || rows <= 0 || n % rows != 0) return SKP_E_BADARG;
+    if (c1 == 0.f) x0_prev = nullptr;
+    if (cn == 0.f) noise = nullptr;
+    const StepCoef c{guidance, sa, sb, cx, c0, ce, c1, cn, (float)((double)sb / (double)sa), prediction, clip ? 1 : 0};
+    return step_launch(true, x, m_c, m_u, x0_prev, noise, y, x0_out, n, copies, c, stream, g, gs, rows);
 }
 
 // y[i] = a * x[i] + b * z[i], i < n (y may be x or z).  The eta = 0 DDIM update with clip_sample off is exactly this.

@@ -5,6 +5,7 @@ h = lambda' - lambda and r = h_prev / h:
 
     m        = m_u + g (m_c - m_u)   or   m_c
     (x0,eps) from (x, m) by the prediction type with (sa, sb) = (alpha_t, sigma_t)        the three cases of DDIMScheduler.step
+    (x0,eps) = (x0 - (sigma / alpha) s g, eps + s g)   with keypoint guidance: g = dE/dx, s the per-image scale (ptp_utils.py)
     x0c      = clamp(x0, -1, 1) if clip_sample else x0                                    (eps stays as derived before the clamp)
     y        = cx x + c0 x0c + ce eps + c1 x0_prev + cn noise,        x0_prev = the previous step's x0c
 
@@ -40,11 +41,12 @@ class StepCoef(NamedTuple):
     cn: float
 
 
-def step_formula(x, m_c, m_u, coef, guidance, prediction_type, clip, x0_prev=None, noise=None):
+def step_formula(x, m_c, m_u, coef, guidance, prediction_type, clip, x0_prev=None, noise=None, grad=None, grad_scale=None):
     """The update at the top of this file in torch, in the dtype of its inputs -> (y, x0c): what the step kernel
     (`ops.sampler_step`, `ops.ddim_step`) computes, for host tensors and other dtypes.  `m_u` None: no guidance.  A term whose tensor
     is absent is not evaluated, and neither is `cx x` when `coef.cx` is None (the DDIM form y = c0 x0c + ce eps of
-    `DDIMScheduler.step`; a `0 * x` there would turn a -0 into +0 and an infinite x into NaN)."""
+    `DDIMScheduler.step`; a `0 * x` there would turn a -0 into +0 and an infinite x into NaN).  `grad` (shaped like x) with
+    `grad_scale` ([rows], one per leading row of x): the gradient term of keypoint guidance, applied to (x0, eps) before the clamp."""
     m = m_c if m_u is None else m_u + guidance * (m_c - m_u)
     if prediction_type == "epsilon":
         x0, eps = (x - coef.sb * m) / coef.sa, m
@@ -52,6 +54,9 @@ def step_formula(x, m_c, m_u, coef, guidance, prediction_type, clip, x0_prev=Non
         x0, eps = coef.sa * x - coef.sb * m, coef.sa * m + coef.sb * x
     else:
         x0, eps = m, (x - coef.sa * m) / coef.sb
+    if grad is not None:
+        sg = grad_scale.reshape((-1,) + (1,) * (grad.dim() - 1)) * grad
+        x0, eps = x0 - (coef.sb / coef.sa) * sg, eps + sg
     if clip:
         x0 = x0.clamp(-1, 1)
     y = coef.c0 * x0 + coef.ce * eps if coef.cx is None else coef.cx * x + coef.c0 * x0 + coef.ce * eps

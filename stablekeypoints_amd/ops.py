@@ -40,7 +40,7 @@ _plans = {}
 def _plan(name: str):
     """(the entry, what each of its arguments before the stream takes) from the table of `_native`; made once per entry."""
     slots = tuple((t.dtype or _ANY) if issubclass(t, N.DevicePointer) else _INT if t in (N._i, N._i64) else _HOST
-                  for t in N.SIGNATURES[name][:-1])
+                  for t in N.signature(name)[:-1])
     _plans[name] = plan = (getattr(N.lib(), name), slots)
     return plan
 
@@ -606,6 +606,75 @@ class MapLossesFn(torch.autograd.Function):
         ge = z if go_equiv is None else go_equiv.reshape(()).float()
         G = torch.cat([gs * g_sharp + ge * g_eq_a, ge * g_eq_b], dim=0)            # [B,K,R,R]
         dS = _map_bwd_sparse(S, sides, B, H, T, R, torch.cat([sel_all, sel_all], dim=0), G, lse)
+        return (None, *_dqk_from_dS(qs, ks, dS, scales, H, T, ctx.needs_input_grad[1:]))
+
+
+def point_loss(M, pos, sigma: float):
+    """Energy of K maps per image against gaussian targets at given positions (csrc/skp_point_loss.hip, formula in
+    include/skp_keypoints.h): M [B,K,R,R], pos [B,K,2] (row, col) in image fractions, on the device -> (E [B] = mean_{k,r,c} (M - t)^2,
+    G [B,K,R,R] = dE[b] / dM[b]).  No autograd; one kernel and one fixed-order sum of its chunk sums: the same bits from call to call."""
+    M, pos = _dev(M.detach(), "M"), _dev(pos.detach(), "pos")
+    if M.dim() != 4 or M.shape[2] != M.shape[3] or tuple(pos.shape) != (M.shape[0], M.shape[1], 2):
+        raise RuntimeError(f"point_loss: maps {tuple(M.shape)} must be [B,K,R,R] and positions {tuple(pos.shape)} [B,K,2]")
+    B, K, R, _ = M.shape
+    partial = torch.empty(B, K, (R * R + 1023) // 1024, device=M.device, dtype=torch.float32)
+    G = torch.empty_like(M)
+    _launch("skp_point_loss_f32", M, pos, B, K, R, float(sigma), partial, G)
+    return partial.sum(dim=(1, 2)) / float(K * R * R), G
+
+
+class MapPointLossFn(torch.autograd.Function):
+    """One node for `maps of K tokens -> energy against caller-given positions` (keypoint guidance of image sampling,
+    ptp_utils.keypoint_energy_grad), the sibling of MapLossesFn: the map backward sees K rows per batch row, not a dense [B,T,R,R].
+        forward : logits -> fused maps (+ lse): the K rows alone where the wide kernel serves the shape, else all rows and a gather
+                  -> point-loss kernel (energy and unit gradient)
+        backward: G = go[b] * g[b] -> the sparse map backward where `map_bwd_sparse_supported`, else the rows scattered into a dense
+                  gradient for the dense kernels -> dq_l (dk_l only if asked for: the context usually needs no gradient).
+    apply(meta, q_0, k_0, q_1, k_1, ...); meta = dict(R, heads, scales, sigma, pos [B,K,2] float32 on the device, sel int64 [K]
+    on the device: K distinct token ids, tokrow int32 [T] on the device: the output row of a token or -1).  Returns E [B]."""
+
+    @staticmethod
+    def forward(ctx, meta, *qk: torch.Tensor):
+        L = len(qk) // 2
+        qs = [_dev(qk[2 * i], "q") for i in range(L)]
+        ks = [_dev(qk[2 * i + 1], "k") for i in range(L)]
+        R, H, scales = int(meta["R"]), int(meta["heads"]), tuple(float(v) for v in meta["scales"])
+        B, T = qs[0].shape[0], ks[0].shape[1]
+        sel, pos, tokrow = meta["sel"], meta["pos"], meta["tokrow"]
+        K = sel.shape[0]
+        if len(scales) != L or tuple(pos.shape) != (B, K, 2) or tuple(tokrow.shape) != (T,):
+            raise RuntimeError("MapPointLossFn: one scale per layer, positions [B,K,2] and a row table of T tokens")
+        sides = []
+        for q, k in zip(qs, ks):
+            s_ = int(round(q.shape[1] ** 0.5))
+            if s_ * s_ != q.shape[1] or q.shape[0] != B or k.shape[1] != T or q.shape[2] % H or k.shape[2] != q.shape[2]:
+                raise RuntimeError("MapPointLossFn: hooked layers disagree on batch rows / token count / head split")
+            sides.append(s_)
+        S = [qk_logits(q, k, H, sc) for q, k, sc in zip(qs, ks, scales)]
+        if map_wide_supported(T, R, sides):
+            M, lse = _map_fwd(S, sides, B, H, T, R, tokrow=tokrow, n_rows=K)
+        else:
+            M, lse = _map_fwd(S, sides, B, H, T, R)
+            M = M.index_select(1, sel)
+        E, G = point_loss(M, pos, float(meta["sigma"]))
+        ctx.save_for_backward(lse, sel, G, *qs, *ks, *S)
+        ctx.meta = (R, H, scales, tuple(sides), B, T, L)
+        return E
+
+    @staticmethod
+    def backward(ctx, go):
+        R, H, scales, sides, B, T, L = ctx.meta
+        saved = ctx.saved_tensors
+        lse, sel, G = saved[:3]
+        qs, ks, S = saved[3:3 + L], saved[3 + L:3 + 2 * L], saved[3 + 2 * L:]
+        K = sel.shape[0]
+        G = go.reshape(B, 1, 1, 1).float() * G
+        if map_bwd_sparse_supported(sides, K, R, T, H):
+            dS = _map_bwd_sparse(S, sides, B, H, T, R, sel.expand(B, K), G, lse)
+        else:
+            dM = torch.zeros(B, T, R, R, device=G.device, dtype=torch.float32).index_copy_(1, sel, G)
+            dS = [torch.empty_like(s_) if T <= TOKEN_GROUP else torch.zeros_like(s_) for s_ in S]
+            _map_bwd(S, dS, sides, B, H, T, R, dM, lse)
         return (None, *_dqk_from_dS(qs, ks, dS, scales, H, T, ctx.needs_input_grad[1:]))
 
 
@@ -1306,8 +1375,11 @@ def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
             return y
         return Conv3x3Fn.apply(x, weight, bias, residual)
     if (frozen and residual is None and x.is_cuda and x.dtype == torch.float32 and CONV3X3_MODE != "lib"
-            and weight.shape[1] <= 4 and x.shape[3] % 2 == 0 and not (torch.is_grad_enabled() and x.requires_grad)):
-        return conv3x3_small(x, weight, bias, want_stats=want_stats)   # conv_in layers: output-bandwidth bound, own VALU kernel
+            and weight.shape[1] <= 4 and x.shape[3] % 2 == 0):
+        if not (torch.is_grad_enabled() and x.requires_grad):
+            return conv3x3_small(x, weight, bias, want_stats=want_stats)   # conv_in layers: output-bandwidth bound, own VALU kernel
+        if conv_in_grad_ok(x, weight):           # the latent takes a gradient (keypoint guidance): its adjoint is a small-output conv
+            return ConvInFn.apply(x, weight, bias)       # (no block statistics: the norm that follows makes its own)
     routes.note("conv_out" if weight.shape[0] <= 8 else "conv3x3", "lib")     # (<= 8 output channels = a conv_out, by the rule above)
     if residual is None:
         return torch.nn.functional.conv2d(x, weight, bias, padding=1)
@@ -1414,9 +1486,40 @@ def conv3x3_small_out(x, weight, bias=None, image=False):
 
 def conv3x3_small_out_ok(x, weight) -> bool:
     """Shapes `conv3x3_small_out` takes: Cin % 16 == 0, Cout <= 4, even width, 3x3 taps."""
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and CONV3X3_MODE != "lib"
-            and int(weight.shape[1]) == x.shape[1] and x.shape[1] % 16 == 0 and weight.shape[0] <= 4 and x.shape[3] % 2 == 0
-            and x.shape[0] <= 65535)
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and int(weight.shape[1]) == x.shape[1]
+            and _small_out_shape_ok(x.shape[0], x.shape[1], weight.shape[0], x.shape[3], weight.shape[2:]))
+
+
+def _small_out_shape_ok(B, ci, co, W, taps) -> bool:
+    return tuple(taps) == (3, 3) and CONV3X3_MODE != "lib" and ci % 16 == 0 and co <= 4 and W % 2 == 0 and B <= 65535
+
+
+def conv_in_grad_ok(x, weight) -> bool:
+    """Whether the input gradient of `conv3x3_small(x, weight)` -- a 3x3 convolution of dy [B,Cout,H,W] to <= 4 channels with the
+    flipped, transposed filter [Cin,Cout,3,3] -- is a shape `conv3x3_small_out` takes."""
+    return x.dim() == 4 and _small_out_shape_ok(x.shape[0], weight.shape[0], weight.shape[1], x.shape[3], weight.shape[2:])
+
+
+class ConvInFn(torch.autograd.Function):
+    """`conv3x3_small` for an input that takes a gradient (the latent under keypoint guidance): the forward is that kernel, the
+    backward the small-output kernel on dy with the flipped, transposed filter, made once per frozen weight.  No weight or bias
+    gradient (frozen blocks only)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.weight = weight
+        return conv3x3_small(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        w = ctx.weight
+        wt = cached(w, "conv_in_bwd", [w], lambda: w.detach().flip(2, 3).transpose(0, 1).contiguous())
+        dy = _dev(dy, "dy")
+        B, co, H, W = dy.shape
+        routes.note("conv_in.bwd_data", "small_out")
+        dx = torch.empty(B, wt.shape[0], H, W, device=dy.device, dtype=torch.float32)
+        _launch("skp_conv3x3_small_out_f32", dy, wt, None, dx, B, co, wt.shape[0], H, W, False)
+        return dx, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1523,13 +1626,16 @@ def ddim_step(x, m_c, m_u=None, *, sa: float, sb: float, pa: float, pb: float, g
 
 
 def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: float = 1.0, prediction="epsilon",
-                 clip: bool = False, copies: int = 1, out=None, x0_out=None):
+                 clip: bool = False, copies: int = 1, out=None, x0_out=None, grad=None, grad_scale=None):
     """One step of a sampler of ldm/samplers.py in one pass (csrc/skp_sampler_step.hip, formula in include/skp.h): the guidance mix,
     (x0, eps) by `prediction` and the clamp as in `ddim_step`, then y = cx x + c0 x0 + ce eps + c1 x0_prev + cn noise with
     `coef` = (sa, sb, cx, c0, ce, c1, cn) (a `samplers.StepCoef`).  -> y shaped like x, or with `copies=2` like torch.cat([x, x]).
     `x0_prev` / `noise`: shaped like x; each may be None when its coefficient is 0.  `out`: as in `ddim_step` (it may be x, or
     a doubled buffer whose first half x is).  `x0_out`: a contiguous float32 tensor shaped like x that receives the clamped x0; it
-    may be `x0_prev` itself (the history updated in place)."""
+    may be `x0_prev` itself (the history updated in place).
+    `grad` (shaped like x) with `grad_scale` (float32 [rows] on the device, rows = x.shape[0]): the gradient term of keypoint
+    guidance, eps += s g and x0 -= (sb / sa) s g before the clamp (skp_sampler_step_kp_f32, include/skp_keypoints.h); the scales
+    are read by the kernel, never by the host."""
     x, m_c, m_u, noise, pred, n, out = _step_args("sampler_step", x, m_c, m_u, x0_prev, noise, prediction, copies, out)
     sa, sb, cx, c0, ce, c1, cn = (float(v) for v in coef)
     if (c1 != 0.0 and x0_prev is None) or (cn != 0.0 and noise is None):
@@ -1537,6 +1643,16 @@ def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: 
     if x0_out is not None and not (x0_out.is_cuda and x0_out.dtype == torch.float32 and x0_out.is_contiguous()
                                    and x0_out.numel() == n):
         raise RuntimeError("sampler_step: `x0_out` must be a contiguous float32 device tensor of x.numel() elements")
+    if (grad is None) != (grad_scale is None):
+        raise ValueError("sampler_step: `grad` and `grad_scale` go together")
+    if grad is not None:
+        grad, grad_scale = _dev(grad, "grad"), _dev(grad_scale, "grad_scale")
+        rows = x.shape[0] if x.dim() else 1
+        if grad.shape != x.shape or tuple(grad_scale.shape) != (rows,):
+            raise RuntimeError(f"sampler_step: `grad` must be shaped like x and `grad_scale` be [{rows}]")
+        _launch("skp_sampler_step_kp_f32", x, m_c, m_u, x0_prev, noise, out, x0_out, n, copies, float(guidance), pred, sa, sb, cx, c0,
+                ce, c1, cn, bool(clip), grad, grad_scale, rows)
+        return out
     _launch("skp_sampler_step_f32", x, m_c, m_u, x0_prev, noise, out, x0_out, n, copies, float(guidance), pred, sa, sb, cx, c0, ce,
             c1, cn, bool(clip))
     return out

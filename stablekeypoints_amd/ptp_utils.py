@@ -5,7 +5,8 @@ Kept names/signatures: `AttentionControl`, `AttentionStore`,
 `find_top_k_gaussian`, `furthest_point_sampling`, `init_random_noise`, and the image-sampling entries `diffusion_step`,
 `latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461); `init_latents` and
 `guided_latent_step` are this port's batched / classifier-free-guidance companions of the last two, `sampler_latent_step` the step
-of the named samplers (ldm/samplers.py).
+of the named samplers (ldm/samplers.py), `keypoint_energy_grad` the energy and latent gradient of keypoint guidance
+(`text2image_ldm_stable(keypoints=...)`).
 
 What changes under the hood
   * the hooked cross-attention does NOT up-sample the layer input, re-project it and materialise a
@@ -21,7 +22,7 @@ from __future__ import annotations
 
 import abc
 import contextlib
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -31,7 +32,7 @@ from . import ops
 from . import routes
 from .ldm.samplers import SamplerPlan, step_formula
 from .ldm.unet import StopForward
-from ._maps import FusedAttn, collect_maps
+from ._maps import FusedAttn, _materialize_host, collect_maps
 
 
 # ---------------------------------------------------------------------------------------------
@@ -356,9 +357,10 @@ def run_and_find_attn(ldm, image, context, noise_level=-1, device="cuda",
 # ---------------------------------------------------------------------------------------------
 # image sampling from a learned embedding                reference ptp_utils.py:307-349,420-461
 # ---------------------------------------------------------------------------------------------
-def _unet_forward_shared_context(model, latents, t, context):
+def _unet_forward_shared_context(model, latents, t, context, records=None):
     """One full UNet forward with the learned embedding as the context of every row (k / v projected once per layer width for
-    the shared row, as in `find_pred_noise`)."""
+    the shared row, as in `find_pred_noise`).  `records` (a list): receives what the hooks stored during this forward, before the
+    store is emptied."""
     b = latents.shape[0]
     try:
         _context_kv_begin(model.unet, context, early_exit=False)
@@ -367,6 +369,8 @@ def _unet_forward_shared_context(model, latents, t, context):
         _context_kv_end()
         hooked = model.unet.__dict__.get("_skp_hook_controller")
         if hooked is not None and hasattr(hooked, "reset"):
+            if records is not None:
+                records.extend(hooked.step_store["attn"])
             hooked.reset()                           # maps the hooks recorded during this forward belong to no optimisation step
 
 
@@ -430,21 +434,120 @@ def init_latents(latent, model, height, width, generators):
     return latent, latent.to(model.device)
 
 
-def _predict(model, latents, context, t, doubled):
+def _predict(model, latents, context, t, doubled, records=None):
     """The UNet forward(s) of one sampling step -> (latents [n, C, h, w], pred_c, pred_u).  `context = [uncond, cond]`: `uncond`
     None -- the conditional prediction alone (pred_u None); contexts of equal length -- ONE forward of 2n rows, the unconditional
-    rows first (`doubled`: `latents` already holds the n rows twice); otherwise two forwards of n rows."""
+    rows first (`doubled`: `latents` already holds the n rows twice); otherwise two forwards of n rows.  `records` (a list):
+    receives the hooked records of the forward that holds the conditional rows (its last n rows, in the one-forward case); the
+    unconditional forward of the two-forward case then runs without autograd."""
     uncond, cond = context
     if uncond is None:
-        return latents, _unet_forward_shared_context(model, latents, t, cond), None
+        return latents, _unet_forward_shared_context(model, latents, t, cond, records), None
     if uncond.shape[1] != cond.shape[1]:
-        pred_u = _unet_forward_shared_context(model, latents, t, uncond)
-        return latents, _unet_forward_shared_context(model, latents, t, cond), pred_u
+        with torch.no_grad() if records is not None else contextlib.nullcontext():
+            pred_u = _unet_forward_shared_context(model, latents.detach() if records is not None else latents, t, uncond)
+        return latents, _unet_forward_shared_context(model, latents, t, cond, records), pred_u
     n = latents.shape[0] // 2 if doubled else latents.shape[0]
     rows = latents if doubled else torch.cat([latents, latents])
     ctx = torch.cat([uncond.expand(n, -1, -1), cond.expand(n, -1, -1)])
-    pred = _unet_forward_shared_context(model, rows, t, ctx)
+    pred = _unet_forward_shared_context(model, rows, t, ctx, records)
     return rows[:n], pred[n:], pred[:n]
+
+
+class KeypointTargets(NamedTuple):
+    """The checked arguments of keypoint guidance on the device, made once per call (`_keypoint_targets`)."""
+    pos: torch.Tensor                        # [n, K, 2] float32 (row, col) in image fractions, on the latents' device
+    ids: list                                # the K token ids, host ints
+    sel: torch.Tensor                        # the same, int64 [K] on the device
+    tokrow: torch.Tensor                     # int32 [T] on the device: the map row of a token, -1 for the others
+
+
+def _keypoint_ids(keypoints, keypoint_indices, T):
+    """Everything about the pair that does not depend on the number of images -> (pos [K, 2] or [m, K, 2] float32 on the host,
+    ids: K host ints).  Reads `keypoint_indices` to the host once; ValueError for one without the other, positions that are not K
+    (row, col) pairs, an index outside the T tokens or listed twice."""
+    if (keypoints is None) != (keypoint_indices is None):
+        raise ValueError("keypoints and keypoint_indices go together: K positions for K token ids")
+    ids = [int(v) for v in torch.as_tensor(keypoint_indices).reshape(-1).tolist()]
+    pos = torch.as_tensor(keypoints).detach().to("cpu", torch.float32)
+    if pos.dim() not in (2, 3) or not ids or tuple(pos.shape[-2:]) != (len(ids), 2):
+        raise ValueError(f"keypoints {tuple(pos.shape)} must be [K, 2] or [n, K, 2] with K = {len(ids)} token ids")
+    if min(ids) < 0 or max(ids) >= T:
+        raise ValueError(f"keypoint_indices {ids} reach outside the embedding's {T} tokens")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"keypoint_indices {ids} must be distinct")
+    return pos, ids
+
+
+def _keypoint_targets(pos, ids, n, T, device):
+    """(pos, ids) of `_keypoint_ids` for n images -> KeypointTargets; ValueError when [m, K, 2] positions are not n rows."""
+    if pos.dim() == 2:
+        pos = pos[None].expand(n, -1, -1)
+    if pos.shape[0] != n:
+        raise ValueError(f"keypoints {tuple(pos.shape)}: {pos.shape[0]} rows of targets for {n} images")
+    tokrow = torch.full((T,), -1, dtype=torch.int32)
+    tokrow[ids] = torch.arange(len(ids), dtype=torch.int32)
+    return KeypointTargets(pos.to(device).contiguous(), ids, torch.tensor(ids, dtype=torch.int64).to(device), tokrow.to(device))
+
+
+def keypoint_energy_grad(model, latents, context, t, keypoints, indices, sigma, layers=(0, 1, 2, 3), doubled=False):
+    """Energy of keypoint guidance and its gradient by the latents at one timestep -> (pred_c, pred_u, E [n], g [n, C, h, w]).
+    Runs the UNet forward(s) of `_predict` (`context = [uncond or None, cond]`, `doubled` as in `sampler_latent_step`) with autograd
+    on, on a detached copy of `latents`; the maps M_i [K, R, R] of image i are the mean over the stored up-block cross layers
+    `layers` and their heads of the up-res softmax maps of its CONDITIONAL row, for the tokens `indices` (K ids; what
+    `collect_maps_batched(controller, indices=)` returns); E_i = mean (M_i - t_i)^2 against the gaussians of width `sigma` (in map
+    pixels) at `keypoints` [K, 2] or [n, K, 2] ((row, col) in image fractions: `optimize_token.gaussian_circle`), the reference's
+    `find_gaussian_loss_at_point` with one point per token; g_i = dE_i / dx_i.  The unconditional rows carry no loss; contexts of
+    unequal length run the unconditional forward without autograd.  The predictions come back detached, the hooked store empty.
+    float32 device tensors take one node, `ops.MapPointLossFn` (fused maps for K rows, the point-loss kernel, the sparse map
+    backward), and the HIP backward of the frozen UNet; host tensors and other dtypes the same formulas in torch ops, so the call
+    runs on an fp64 copy of the modules on the host.  The model must be hooked (`register_attention_control`, as `load_ldm`
+    does)."""
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    T = context[1].shape[1]
+    targets = _keypoint_targets(*_keypoint_ids(keypoints, indices, T), n, T, latents.device)
+    return _energy_grad(model, latents, context, t, targets, sigma, layers, doubled)
+
+
+def _energy_grad(model, latents, context, t, targets, sigma, layers=(0, 1, 2, 3), doubled=False):
+    """`keypoint_energy_grad` for prepared `KeypointTargets` (the sampling loop makes them once, before its first step)."""
+    hooked = model.unet.__dict__.get("_skp_hook_controller")
+    if hooked is None or not hasattr(hooked, "step_store"):
+        raise RuntimeError("keypoint_energy_grad: the UNet carries no attention store (register_attention_control / load_ldm)")
+    uncond, cond = context
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    pos, ids, sel, tokrow = targets
+    hooked.reset()
+    records = []
+    with torch.enable_grad():
+        x = latents.detach().requires_grad_()
+        _, pred_c, pred_u = _predict(model, x, context, t, doubled, records)
+        chosen = [r for i, r in enumerate(records) if i in layers]
+        if not chosen or not all(isinstance(r, FusedAttn) for r in chosen):
+            raise RuntimeError("keypoint_energy_grad: no stored attention layer matches `layers` (or the store materialises its "
+                               "entries: AttentionStore(materialize=True) keeps no autograd history)")
+        R, heads = chosen[0].R, chosen[0].heads
+        qs = [r.q[-n:] for r in chosen]                                       # the conditional rows are the last n of the forward
+        ks = [r.k if r.k.shape[0] == 1 else r.k[-n:] for r in chosen]
+        if x.is_cuda and x.dtype == torch.float32:
+            routes.note("sample.keypoints", "map_point_loss")
+            meta = dict(R=R, heads=heads, scales=[r.scale for r in chosen], sigma=float(sigma), pos=pos, sel=sel, tokrow=tokrow)
+            E = ops.MapPointLossFn.apply(meta, *[v for q, k in zip(qs, ks) for v in (q, k)])
+        else:
+            routes.note("sample.keypoints", "host")
+            M = 0
+            for r, q, k in zip(chosen, qs, ks):
+                probs = _materialize_host(q, k, heads, r.scale, R)            # (n * heads, R^2, T)
+                M = M + probs.reshape(n, heads, R * R, -1)[..., ids].mean(dim=1)
+            M = (M / len(chosen)).permute(0, 2, 1).reshape(n, len(ids), R, R)
+            p = pos.to(M.dtype) * R
+            ar = torch.arange(R, device=M.device, dtype=M.dtype) + 0.5
+            d2 = (ar.view(1, 1, 1, R) - p[..., 1, None, None]) ** 2 + (ar.view(1, 1, R, 1) - p[..., 0, None, None]) ** 2
+            E = ((M - torch.exp(-d2 / (2.0 * float(sigma) ** 2))) ** 2).mean(dim=(1, 2, 3))
+        g, = torch.autograd.grad(E.sum(), x)
+    if doubled:
+        g = g[n:]
+    return pred_c.detach(), None if pred_u is None else pred_u.detach(), E.detach(), g
 
 
 def _finish(controller, out, doubled):
@@ -490,7 +593,8 @@ def latent_step(model, controller, latents, context, t, guidance_scale, low_reso
     return _finish(controller, model.scheduler.step(noise_pred, t, latents)["prev_sample"], False)
 
 
-def sampler_latent_step(model, controller, latents, context, t, guidance_scale, *, plan, coef, x0_hist, noise=None, doubled=False):
+def sampler_latent_step(model, controller, latents, context, t, guidance_scale, *, plan, coef, x0_hist, noise=None, doubled=False,
+                        preds=None, grad=None, grad_scale=None):
     """One step of a sampler of ldm/samplers.py: the UNet forward(s) of `latent_step` (`context[0]` None: the conditional prediction
     alone) or of `guided_latent_step` (one forward of 2n rows for contexts of equal length, two forwards otherwise; `doubled` as
     there), then the sampler's linear update with the host numbers `coef` (a `samplers.StepCoef` of `plan`, whose prediction type
@@ -498,21 +602,29 @@ def sampler_latent_step(model, controller, latents, context, t, guidance_scale, 
     `coef.c1 != 0` and overwritten in place with this step's (the multistep solvers only; None for "ddim").  `noise` [n, C, h, w]:
     this step's gaussian, read when `coef.cn != 0`.  float32 device tensors take one kernel, `ops.sampler_step`, that also
     writes the second copy of a doubled result; host tensors and other dtypes evaluate the same formula in torch, in the input
-    dtype."""
+    dtype.  `preds` = (pred_c, pred_u): this step's predictions, already made (`keypoint_energy_grad`) -- no forward runs here;
+    `grad` [n, C, h, w] with `grad_scale` [n] (on the latents' device, never read back): the gradient term of keypoint guidance,
+    eps += s g and x0 -= (sb / sa) s g before the clamp (`samplers.step_formula`)."""
     uncond, cond = context
     guided = uncond is not None
     if doubled and not (guided and uncond.shape[1] == cond.shape[1]):
         raise ValueError("sampler_latent_step: doubled latents need guidance with contexts of equal length")
-    latents, pred_c, pred_u = _predict(model, latents, context, t, doubled)
+    if preds is None:
+        latents, pred_c, pred_u = _predict(model, latents, context, t, doubled)
+    else:
+        latents, (pred_c, pred_u) = latents[:latents.shape[0] // 2] if doubled else latents, preds
     prev = x0_hist if coef.c1 != 0 else None
     nz = noise if coef.cn != 0 else None
-    if latents.is_cuda and all(v is None or v.dtype == torch.float32 for v in (latents, pred_c, pred_u, prev, nz, x0_hist)):
+    if latents.is_cuda and all(v is None or v.dtype == torch.float32 for v in (latents, pred_c, pred_u, prev, nz, x0_hist, grad,
+                                                                               grad_scale)):
         routes.note("sample.step", "sampler_step")
         out = ops.sampler_step(latents, pred_c, pred_u, x0_prev=prev, noise=nz, coef=coef, guidance=float(guidance_scale),
-                               prediction=plan.prediction_type, clip=plan.clip_sample, copies=2 if doubled else 1, x0_out=x0_hist)
+                               prediction=plan.prediction_type, clip=plan.clip_sample, copies=2 if doubled else 1, x0_out=x0_hist,
+                               grad=grad, grad_scale=grad_scale)
     else:
         routes.note("sample.step", "host")
-        out, x0 = step_formula(latents, pred_c, pred_u, coef, guidance_scale, plan.prediction_type, plan.clip_sample, prev, nz)
+        out, x0 = step_formula(latents, pred_c, pred_u, coef, guidance_scale, plan.prediction_type, plan.clip_sample, prev, nz,
+                               grad, grad_scale)
         if x0_hist is not None:
             x0_hist.copy_(x0)
         out = torch.cat([out, out]) if doubled else out
@@ -582,7 +694,9 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                           generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
                           height: int = 512, width: int = 512, output_type: str = "uint8",
                           uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None,
-                          sampler: Optional[str] = None, eta: float = 0.0):
+                          sampler: Optional[str] = None, eta: float = 0.0, keypoints=None, keypoint_indices=None,
+                          keypoint_scale: float = 2.0, keypoint_sigma: float = 2.0, keypoint_steps=(0.0, 1.0),
+                          keypoint_normalize: bool = True, keypoint_trace: Optional[list] = None):
     """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` steps of `sampler`
     (deterministic DDIM by default) and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
@@ -609,9 +723,24 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     before the loop, image i's from `generator[i]` after its initial latent, one torch.randn((1, C, h, w)) per step -- image i
     of a batch sees the noise of the single-image call with that generator -- and upload it once as [steps, n, C, h, w]; they
     need a generator also when `latent` is given (ValueError otherwise).
-    The loop is not captured into a graph.  NOT reproduced: the reference's `torch.load` of two hard-coded files
-    ("example_attn_maps_indices.pt", "outputs/indices.pt", whose contents it never uses) and
-    `register_attention_control_generation`, which re-installs the attention math the module tree already computes.  `height`,
+    Keypoint guidance (keyword-only extension): `keypoints` [K, 2] (the same targets for every image) or [n, K, 2], (row, col) in
+    image fractions (positions outside [0, 1] are legal), with `keypoint_indices`, K distinct token ids of the embedding -- the
+    tensor `find_best_indices` returns, the reference's "outputs/indices.pt" -- samples an image whose learned keypoints sit where the
+    caller puts them: what the reference's generation script was meant to do with the two files it loads
+    ("example_attn_maps_indices.pt", "outputs/indices.pt") and then never uses.  At every step i of N with lo <= i / N < hi
+    (`keypoint_steps` = (lo, hi)) `keypoint_energy_grad` gives E_i = mean (M_i - t_i)^2 -- M_i the K up-res cross-attention maps of
+    image i's conditional row at this step, t_i gaussians of width `keypoint_sigma` map pixels at the targets -- and
+    g_i = dE_i / dx_i by one backward through the frozen UNet; the step then shifts eps by s_i g_i and x0 by -(sb / sa) s_i g_i
+    before the clamp and the sampler's update, with s_i = keypoint_scale sb_t / max(rms(g_i), 1e-12) (`keypoint_normalize`, the rms over
+    C h w) or keypoint_scale sb_t.  The scales stay on the device; nothing in the loop is read back.  `keypoint_trace`: a list
+    that receives each guided step's E [n] (a device tensor).  With keypoints the loop always runs `sampler_latent_step`
+    (`sampler=None` takes the "ddim" eta = 0 plan there) -- guided, doubled, batched or not, for every sampler and prediction type;
+    a guided step costs about one optimisation step's forward and backward for n rows on top.  The default scale of 2 was only
+    tried on the seeded reduced-width tree of the tests, never on trained weights.  ValueError: one of the two without the other,
+    a shape mismatch, an index outside the embedding (or twice).  Without `keypoints` nothing changes: the same routes, the same
+    bits.
+    The loop is not captured into a graph.  NOT reproduced: `register_attention_control_generation`, which re-installs the
+    attention math the module tree already computes.  `height`,
     `width` and `output_type` are keyword-only extensions (the reference fixes 512 x 512).  The scheduler's timestep table is
     restored afterwards, so a sampling call between optimisation steps does not move their noise level.  The model must have
     been loaded with its VAE decoder (`load_ldm(..., decoder=True)`)."""
@@ -642,6 +771,10 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
         uncond_embedding = encode_prompt(model, [uncond_prompt])
         if isinstance(uncond_embedding, tuple):                    # SDXL: (context, pooled); the pooled vector is not fed to sampling
             uncond_embedding = uncond_embedding[0]
+    targets = None
+    if keypoints is not None or keypoint_indices is not None:           # (checked before anything is drawn from a generator)
+        targets = _keypoint_ids(keypoints, keypoint_indices, embedding.shape[1])
+        lo, hi = (float(v) for v in keypoint_steps)
     if isinstance(generator, (list, tuple)) or (latent is not None and latent.dim() == 4 and latent.shape[0] != 1):
         if isinstance(generator, (list, tuple)) and latent is not None and len(generator) != latent.shape[0]:
             raise ValueError(f"{len(generator)} generators for a latent of {latent.shape[0]} rows (a given latent is used as it is; "
@@ -659,6 +792,10 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
         if uncond.dim() != 3 or uncond.shape[0] != 1 or uncond.shape[-1] != embedding.shape[-1]:
             raise ValueError(f"uncond_embedding {tuple(uncond_embedding.shape)} must be [1, T, {embedding.shape[-1]}]")
     context = [uncond if guided else None, embedding]
+    if targets is not None:
+        targets = _keypoint_targets(*targets, n, embedding.shape[1], latents.device)
+        if plan is None:
+            plan = SamplerPlan(model.scheduler, "ddim", 0.0)       # the guided step is a term of the sampler kernel
     # on the GPU a guided step with contexts of equal length keeps the 2n-row UNet input between steps (written by the step kernel)
     doubled = guided and latents.is_cuda and uncond.shape[1] == embedding.shape[1]
     if doubled:
@@ -677,9 +814,19 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
             with ops.up2_in_unet(latents.is_cuda):
                 for i, t in enumerate(sched.timesteps if plan is None else timesteps):
                     if plan is not None:
+                        kp = {}
+                        if targets is not None and lo <= i / len(coefs) < hi:
+                            pred_c, pred_u, energy, g = _energy_grad(model, latents, context, t, targets, keypoint_sigma,
+                                                                     doubled=doubled)
+                            s = torch.full_like(energy, float(keypoint_scale) * coefs[i].sb)
+                            if keypoint_normalize:
+                                s = s / g.pow(2).mean(dim=(1, 2, 3)).sqrt().clamp_min(1e-12)
+                            if keypoint_trace is not None:
+                                keypoint_trace.append(energy)
+                            kp = dict(preds=(pred_c, pred_u), grad=g, grad_scale=s)
                         latents = sampler_latent_step(model, controller, latents, context, t, guidance_scale, plan=plan,
                                                       coef=coefs[i], x0_hist=x0_hist, noise=None if noise is None else noise[i],
-                                                      doubled=doubled)
+                                                      doubled=doubled, **kp)
                     elif guided:
                         latents = guided_latent_step(model, controller, latents, context, t, guidance_scale, doubled=doubled)
                     else:

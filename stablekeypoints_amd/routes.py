@@ -40,7 +40,9 @@ ROUTES: Dict[str, Dict[str, str]] = {
     "conv3x3": dict(_WINO),
     # their input gradient (ops.Conv3x3Fn.backward); the zero-stuffed stride-2 gradient runs on the same kernels and counts here too
     "conv3x3.bwd_data": dict(_WINO),
-    "conv_in": {"small": "hip"},                          # <= 4 input channels, forward only (ops.conv3x3_small)
+    "conv_in": {"small": "hip"},                          # <= 4 input channels (ops.conv3x3_small)
+    # its input gradient when the latent takes one (keypoint guidance; ops.ConvInFn): the small-output kernel on the flipped filter
+    "conv_in.bwd_data": {"small_out": "hip"},
     # <= 8 output channels: below the Winograd kernels' channel blocks; the VAE decoder's <= 4 on its own VALU kernel
     "conv_out": {"lib": "library", "small_out": "hip"},
     # Upsample2D of the VAE decoder, and of the UNet inside the sampling loop (ops.conv3x3_up2): polyphase kernel on the
@@ -70,6 +72,9 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # the step of a named sampler (ptp_utils.sampler_latent_step; text2image_ldm_stable(sampler=) other than the eta = 0 DDIM
     # step it always had, which has no gate and notes nothing): the fused step kernel / the formula in torch on host tensors
     "sample.step": {"sampler_step": "hip", "host": "host"},
+    # energy and latent gradient of keypoint guidance (ptp_utils.keypoint_energy_grad): the fused maps + point-loss node
+    # (ops.MapPointLossFn; its map kernels note `map.fwd` / `map.bwd` as well) / torch ops on host tensors and other dtypes
+    "sample.keypoints": {"map_point_loss": "hip", "host": "host"},
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),

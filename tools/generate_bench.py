@@ -3,7 +3,7 @@
 classifier-free guidance, and print the route table of one guided step.
 
     python tools/generate_bench.py [--model synthetic-sd15] [--size 512] [--steps 10] [--n 4] [--rounds 3] [--tokens 77] [--json FILE]
-                                   [--sampler ddim|dpm++2m|dpm++2m-sde [--eta 0] [--sampler-steps K]] [--variants A,G1]
+                                   [--sampler ddim|dpm++2m|dpm++2m-sde [--eta 0] [--sampler-steps K]] [--variants A,G1] [--keypoints]
 
 Every timed call ends in a device synchronise (the uint8 image is copied to the host); every shape is warmed up once before the
 timed rounds; the variants run alternately inside each round, so a drift of the machine shows up as spread, not as a difference.
@@ -14,6 +14,11 @@ timed rounds; the variants run alternately inside each round, so a drift of the 
 `--sampler NAME`: every variant is timed a second time as `<variant>@NAME/K`, sampled by NAME in K = `--sampler-steps` steps (default:
 `--steps`), in turn with the default call at `--steps` -- e.g. `--steps 50 --sampler dpm++2m --sampler-steps 20 --n 1 --variants A,G1`
 times the 20-step DPM-Solver++ image against the 50-step DDIM image, unguided and guided.  `--variants`: only these.
+`--keypoints`: every variant is timed a second time as `<variant>+kp`, the same call with keypoint guidance (K = 10 tokens, targets
+drawn from the seed, every step guided), in turn with the call without it (with `--sampler` also `<variant>@NAME/K+kp`); and `ops.MapPointLossFn` (forward and backward) is
+timed against the route the package had before it -- dense fused maps under autograd, a gather, torch ops for the target and the
+MSE -- on the hooked layers of SD-1.5 at 512^2 (sides 16, 16, 16, 32; 8 heads of 160, 160, 160, 80 channels; R = 128) with
+T = 77 and T = 500 tokens, K = 10, n = 1 and 4 rows.
 Times are per image."""
 import argparse
 import json
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--eta", type=float, default=0.0)
     ap.add_argument("--sampler-steps", type=int, default=None)
     ap.add_argument("--variants", default=None)
+    ap.add_argument("--keypoints", action="store_true")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "generate_bench.py measures the GPU path only"
@@ -78,11 +84,16 @@ def main():
     unknown = [k for k in names if k not in variants]
     if unknown or not names:
         ap.error(f"--variants: unknown {unknown}; choose from {list(variants)}")
-    variants = {k: variants[k] for k in names}
+    overs = {"": {}}                                            # name suffix -> keywords on top of every call's; the two flags compose
     if a.sampler is not None:
         k_steps = a.sampler_steps or a.steps
-        named = make(sampler=a.sampler, eta=a.eta, num_inference_steps=k_steps)
-        variants = {name: fn for k in names for name, fn in ((k, variants[k]), (f"{k}@{a.sampler}/{k_steps}", named[k]))}
+        overs[f"@{a.sampler}/{k_steps}"] = dict(sampler=a.sampler, eta=a.eta, num_inference_steps=k_steps)
+    if a.keypoints:
+        kp_ids = torch.randperm(a.tokens, generator=g)[:10].sort().values
+        kp = dict(keypoints=torch.rand(len(kp_ids), 2, generator=g), keypoint_indices=kp_ids)
+        overs = {name: o for suffix, over in overs.items() for name, o in ((suffix, over), (suffix + "+kp", {**over, **kp}))}
+    made = {suffix: make(**over) for suffix, over in overs.items()}
+    variants = {k + suffix: made[suffix][k] for k in names for suffix in overs}
     width = max([7] + [len(k) for k in variants])
     times = {k: [] for k in variants}
     for k, fn in variants.items():                              # warm-up: every shape once
@@ -109,9 +120,57 @@ def main():
         ctrl.reset()
         tables[2 * rows] = routes.table(routes.delta(before))
         print(f"\nroutes of one guided step, {2 * rows} rows per forward:\n{tables[2 * rows]}")
+    node = node_against_older_route(a.rounds) if a.keypoints else {}
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(args=vars(a), seconds_per_image=times, routes={str(k): v for k, v in tables.items()}), f, indent=1)
+            json.dump(dict(args=vars(a), seconds_per_image=times, routes={str(k): v for k, v in tables.items()},
+                           map_point_loss_seconds=node), f, indent=1)
+
+
+def node_against_older_route(rounds, K=10, R=128, sides=(16, 16, 16, 32), heads=8, widths=(1280, 1280, 1280, 640), calls=20):
+    """Forward + backward (dq) of `ops.MapPointLossFn` against dense `fused_maps` + gather + torch MSE under autograd, on random
+    q / k of the hooked SD-1.5 layers at 512^2; `calls` of each per timed window, the two in turn; -> {shape: {route: [seconds per
+    call]}}."""
+    import torch
+    from stablekeypoints_amd import ops
+    from stablekeypoints_amd._maps import FusedAttn, fused_maps
+    from stablekeypoints_amd.optimize_token import gaussian_circle
+    out = {}
+    for T, n in ((77, 1), (77, 4), (500, 1), (500, 4)):
+        g = torch.Generator().manual_seed(T + n)
+        qs = [torch.randn(n, s * s, c, generator=g).cuda().requires_grad_() for s, c in zip(sides, widths)]
+        ks = [torch.randn(1, T, c, generator=g).cuda() for c in widths]
+        scales = [(c // heads) ** -0.5 for c in widths]
+        ids = torch.randperm(T, generator=g)[:K].sort().values
+        pos = torch.rand(n, K, 2, generator=g).cuda()
+        tokrow = torch.full((T,), -1, dtype=torch.int32)
+        tokrow[ids] = torch.arange(K, dtype=torch.int32)
+        meta = dict(R=R, heads=heads, scales=scales, sigma=2.0, pos=pos, sel=ids.cuda(), tokrow=tokrow.cuda())
+        flat = [v for q, k in zip(qs, ks) for v in (q, k)]
+
+        def node():
+            torch.autograd.grad(ops.MapPointLossFn.apply(meta, *flat).sum(), qs)
+
+        def older():
+            M = fused_maps([FusedAttn(q, k, heads, sc, R) for q, k, sc in zip(qs, ks, scales)])[:, meta["sel"]]
+            t = torch.stack([gaussian_circle(pos[b], size=R, sigma=2.0) for b in range(n)])
+            torch.autograd.grad(((M - t) ** 2).mean(dim=(1, 2, 3)).sum(), qs)
+        fns = {"map_point_loss": node, "older_route": older}
+        times = {k: [] for k in fns}
+        for fn in fns.values():
+            fn()
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) / calls)
+        out[f"T={T} n={n}"] = times
+        print(f"map + point loss, forward and backward, T = {T}, n = {n}: " + ", ".join(
+            f"{k} median {sorted(ts)[len(ts) // 2] * 1e3:.3f} ms (min {min(ts) * 1e3:.3f})" for k, ts in times.items()))
+    return out
 
 
 if __name__ == "__main__":

@@ -5,6 +5,8 @@
                                    [--steps 50] [--seed 0] [--n 1] [--size 512] [--device cuda]
                                    [--uncond unc.pt | --negative-prompt TEXT] [--guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
                                    [--sampler ddim|dpm++2m|dpm++2m-sde] [--eta 0]
+                                   [--keypoints "r,c;r,c;..."|FILE.pt --keypoint-indices FILE.pt|"i,j,..." [--keypoint-scale 2]
+                                    [--keypoint-sigma 2] [--keypoint-steps 0,1]]
 
 `--embedding`: a tensor [1, T, D] (or [T, D]) saved with torch.save -- what `optimize_embedding` returns.  Image i is sampled from
 seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3]).
@@ -17,7 +19,12 @@ text encoder and its tokenizer with the model (tools/encode_prompt.py writes the
 `--prediction-type`: what the UNet predicts; default: the checkpoint's scheduler/scheduler_config.json, else epsilon.
 `--sampler`: ddim (the default), dpm++2m (DPM-Solver++ 2M: try `--steps 20`) or dpm++2m-sde; `--eta` in (0, 1] adds DDIM's variance
 noise (it selects ddim when `--sampler` is not given, and is an error with another sampler);
-the stochastic ones draw their noise from the image's seed, after its starting noise, so an image does not depend on `--batch`."""
+the stochastic ones draw their noise from the image's seed, after its starting noise, so an image does not depend on `--batch`.
+`--keypoints` with `--keypoint-indices`: keypoint guidance -- K target positions (row, col) in image fractions, written out or a
+tensor [K, 2] saved with torch.save (the same targets for every image), for K token ids of the embedding, written out or the
+tensor `find_best_indices` returned (the reference's outputs/indices.pt); `--keypoint-scale`, `--keypoint-sigma` (map pixels) and
+`--keypoint-steps lo,hi` (the guided fraction of the steps) as in `text2image_ldm_stable`.  Prints each image's energy at the first
+and at the last guided step.  The default scale was only tried on the seeded reduced-width tree, never on trained weights."""
 import argparse
 import os
 import sys
@@ -44,6 +51,11 @@ def main():
     ap.add_argument("--prediction-type", default=None, choices=("epsilon", "v_prediction", "sample"))
     ap.add_argument("--sampler", default=None, choices=("ddim", "dpm++2m", "dpm++2m-sde"))
     ap.add_argument("--eta", type=float, default=0.0)
+    ap.add_argument("--keypoints", default=None)
+    ap.add_argument("--keypoint-indices", default=None)
+    ap.add_argument("--keypoint-scale", type=float, default=2.0)
+    ap.add_argument("--keypoint-sigma", type=float, default=2.0)
+    ap.add_argument("--keypoint-steps", default="0,1")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -62,6 +74,23 @@ def main():
     if a.uncond is not None:
         unc = torch.load(a.uncond, map_location="cpu", weights_only=True)
         unc = unc[None] if unc.dim() == 2 else unc
+    if (a.keypoints is None) != (a.keypoint_indices is None):
+        ap.error("--keypoints and --keypoint-indices go together")
+    kp = {}
+    if a.keypoints is not None:
+        def listed(text, number, what):
+            if os.path.exists(text):
+                return torch.load(text, map_location="cpu", weights_only=True)
+            try:
+                return torch.tensor([[number(v) for v in part.split(",")] for part in text.split(";")])
+            except ValueError:
+                ap.error(f"{what}: neither a file nor numbers: {text!r}")
+        window = [float(v) for v in a.keypoint_steps.split(",")]
+        if len(window) != 2:
+            ap.error("--keypoint-steps takes lo,hi")
+        kp = dict(keypoints=listed(a.keypoints, float, "--keypoints").float(),
+                  keypoint_indices=listed(a.keypoint_indices, int, "--keypoint-indices").reshape(-1).long(),
+                  keypoint_scale=a.keypoint_scale, keypoint_sigma=a.keypoint_sigma, keypoint_steps=tuple(window))
     if a.batch < 1:
         ap.error("--batch must be at least 1")
     if not 0.0 <= a.eta <= 1.0:
@@ -84,10 +113,15 @@ def main():
     for first in range(0, a.n, a.batch):
         ids = range(first, min(first + a.batch, a.n))
         gens = [torch.Generator().manual_seed(a.seed + i) for i in ids]
+        trace = []
         image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps, guidance_scale=a.guidance,
                                                    generator=gens[0] if a.batch == 1 else gens, height=a.size, width=a.size,
-                                                   uncond_embedding=unc, uncond_prompt=a.negative_prompt, sampler=a.sampler, eta=a.eta)
+                                                   uncond_embedding=unc, uncond_prompt=a.negative_prompt, sampler=a.sampler, eta=a.eta,
+                                                   keypoint_trace=trace, **kp)
         for row, i in enumerate(ids):
+            if trace:
+                print(f"image {i}: keypoint energy {float(trace[0][row]):.6f} at the first guided step, {float(trace[-1][row]):.6f} "
+                      f"at the last of {len(trace)}")
             path = f"{a.out}_{i}" + (".png" if Image is not None else ".npy")
             if Image is not None:
                 Image.fromarray(image[row]).save(path)
