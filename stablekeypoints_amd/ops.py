@@ -1670,6 +1670,66 @@ def image_u8_nhwc(x):
     return y
 
 
+def map_range(maps):
+    """float [..., h, w] -> [N, 2] = (min, max) of each of the N = prod(leading dims) maps, NaN ignored, (0, 0) for a map of only
+    NaN; exact, whatever the split over workgroups (csrc/skp_overlay.hip, include/skp_overlay.h)."""
+    maps = _dev(maps.detach(), "maps")
+    if maps.dim() < 2 or maps.numel() == 0:
+        raise RuntimeError(f"map_range: expected [..., h, w] with elements, got {tuple(maps.shape)}")
+    plane = maps.shape[-2] * maps.shape[-1]
+    n = maps.numel() // plane
+    out = torch.empty(n, 2, device=maps.device, dtype=torch.float32)
+    ws = _workspace("skp_map_range_workspace", n, plane, device=maps.device)
+    _launch("skp_map_range_f32", maps, out, ws, n, plane)
+    return out
+
+
+def overlay_u8(img, maps=None, rng=None, lut=None, alpha: float = 0.7, pts=None, colors=None, glyphs=None, radius: float = 9.0,
+               ring: float = 1.5, labels: bool = True, out=None, origin=(0, 0), cols: int = 1, gap: int = 0):
+    """Images under an optional colour-mapped heat map and numbered markers, as bytes in a canvas (csrc/skp_overlay.hip; the
+    per-pixel formula is in include/skp_overlay.h and, in torch, `visualize.overlay_formula`).  img [B,3,H,W]; maps [B,S,S] with
+    rng [B,2] (`map_range`) and lut [L,3]; pts [B,K,2] (row, col) in image fractions with colors [K,3] and glyphs uint8 [10,7].
+    `out`: a uint8 canvas [h, w, 3] on the device that image b is written into at origin + (b // cols, b % cols) * (H + gap, W + gap);
+    None allocates [B,H,W,3], one image per tile (cols = 1, gap = 0).  Returns the canvas."""
+    img = _dev(img.detach(), "img")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise RuntimeError(f"overlay_u8: expected [B,3,H,W], got {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    S = L = K = 0
+    if maps is not None:
+        maps, rng, lut = _dev(maps.detach(), "maps"), _dev(rng.detach(), "rng"), _dev(lut.detach(), "lut")
+        if maps.dim() != 3 or maps.shape[0] != B or maps.shape[1] != maps.shape[2] or tuple(rng.shape) != (B, 2) or lut.dim() != 2 \
+                or lut.shape[1] != 3:
+            raise RuntimeError(f"overlay_u8: maps {tuple(maps.shape)} must be [{B},S,S], rng {tuple(rng.shape)} [{B},2], "
+                               f"lut {tuple(lut.shape)} [L,3]")
+        S, L = maps.shape[1], lut.shape[0]
+    else:
+        rng = lut = None
+    if pts is not None and pts.shape[1] > 0:
+        pts, colors = _dev(pts.detach(), "pts"), _dev(colors.detach(), "colors")
+        K = pts.shape[1]
+        if tuple(pts.shape) != (B, K, 2) or tuple(colors.shape) != (K, 3):
+            raise RuntimeError(f"overlay_u8: pts {tuple(pts.shape)} must be [{B},K,2] and colors {tuple(colors.shape)} [K,3]")
+        if labels:
+            if glyphs is None or not glyphs.is_cuda or glyphs.dtype != torch.uint8 or tuple(glyphs.shape) != (10, 7):
+                raise RuntimeError("overlay_u8: labels need glyphs, uint8 [10,7] on the device (there is no CPU fallback)")
+            glyphs = glyphs.contiguous()
+        else:
+            glyphs = None
+    else:
+        pts = colors = glyphs = None
+    if out is None:
+        out, origin, cols, gap = torch.empty(B, H, W, 3, device=img.device, dtype=torch.uint8), (0, 0), 1, 0
+        ch, ld = B * H, W
+    else:
+        if not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 3 or out.shape[2] != 3 or not out.is_contiguous():
+            raise RuntimeError("overlay_u8: out must be a contiguous uint8 canvas [h, w, 3] on the device (there is no CPU fallback)")
+        ch, ld = out.shape[0], out.shape[1]
+    _launch("skp_overlay_u8_f32", img, maps, rng, lut, pts, colors, glyphs, out, B, H, W, S, L, K, float(alpha), float(radius),
+            float(ring), int(bool(labels)), ld, ch, int(origin[0]), int(origin[1]), int(cols), int(gap))
+    return out
+
+
 def mfma_issue_rate(waves_per_simd: int = 1, iters: int = 20000, device=None) -> float:
     """Measurement aid: TFLOP/s of back-to-back independent fp32 MFMAs with `waves_per_simd` waves on every SIMD."""
     import ctypes

@@ -75,6 +75,10 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # energy and latent gradient of keypoint guidance (ptp_utils.keypoint_energy_grad): the fused maps + point-loss node
     # (ops.MapPointLossFn; its map kernels note `map.fwd` / `map.bwd` as well) / torch ops on host tensors and other dtypes
     "sample.keypoints": {"map_point_loss": "hip", "host": "host"},
+    # visualize.overlay: (min, max) of every heat map, and images + maps + points -> bytes in a canvas: the range and overlay
+    # kernels (ops.map_range, ops.overlay_u8) / visualize.range_formula, visualize.overlay_formula in torch on host tensors
+    "visualize.range": {"map_range": "hip", "host": "host"},
+    "visualize.overlay": {"overlay_u8": "hip", "host": "host"},
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),
