@@ -130,13 +130,21 @@ def _materialize_host(q, k, heads, scale, R):
     return S.reshape(B * heads, T, R * R).permute(0, 2, 1).softmax(dim=-1).contiguous()
 
 
+def stack_of(records: List[FusedAttn], who: str, rows=None) -> ops.MapStack:
+    """The checked layer stack of stored records; `rows` (a slice) keeps those batch rows of every q and of every k that is
+    not shared by all rows."""
+    if any(r.R != records[0].R or r.heads != records[0].heads for r in records):
+        raise RuntimeError(f"{who}: hooked layers disagree on feature_upsample_res / head count")
+    qs, ks = [r.q for r in records], [r.k for r in records]
+    if rows is not None:
+        qs, ks = [q[rows] for q in qs], [k if k.shape[0] == 1 else k[rows] for k in ks]
+    return ops.MapStack(who, qs, ks, records[0].heads, [r.scale for r in records], records[0].R)
+
+
 def fused_maps(records: List[FusedAttn]) -> torch.Tensor:
     """[B,T,R,R] = mean over (layer, head) of the up-res softmax maps (one kernel launch)."""
-    R, heads = records[0].R, records[0].heads
-    for r in records:
-        if r.R != R or r.heads != heads:
-            raise RuntimeError("hooked layers disagree on feature_upsample_res / head count")
-    return ops.attn_map([r.q for r in records], [r.k for r in records], heads, [r.scale for r in records], R)
+    st = stack_of(records, "fused_maps")
+    return ops.AttnMapFn.apply(st.R, st.heads, st.scales, *st.flat())
 
 
 def collect_maps(controller, from_where=["up_cross"], upsample_res=512, layers=[0, 1, 2, 3], indices=None):
@@ -149,11 +157,8 @@ def collect_maps(controller, from_where=["up_cross"], upsample_res=512, layers=[
         raise RuntimeError("collect_maps: no stored attention layer matches `layers`")
     if all(isinstance(r, FusedAttn) for r in chosen):
         if indices is not None and not torch.is_grad_enabled():  # inference: only the asked-for rows are computed / written
-            for r in chosen:
-                if r.R != chosen[0].R or r.heads != chosen[0].heads:
-                    raise RuntimeError("hooked layers disagree on feature_upsample_res / head count")
-            m = ops.attn_map_rows([r.q for r in chosen], [r.k for r in chosen], chosen[0].heads,
-                                  [r.scale for r in chosen], chosen[0].R, indices).mean(dim=0)
+            st = stack_of(chosen, "collect_maps")
+            m = ops.attn_map_rows(st.qs, st.ks, st.heads, st.scales, st.R, indices).mean(dim=0)
         else:
             m = fused_maps(chosen).mean(dim=0)                    # mean over the batch rows (B*h axis)
             if indices is not None:
@@ -195,10 +200,7 @@ def collect_maps_batched(controller, layers=(0, 1, 2, 3), indices=None) -> torch
         # the row-selecting kernel path is inference only (it detaches q / k): with autograd on, gather differentiably
         out = fused_maps(chosen)[:, torch.as_tensor(indices, device=chosen[0].q.device).long()]
     else:
-        R, heads = chosen[0].R, chosen[0].heads
-        for r in chosen:
-            if r.R != R or r.heads != heads:
-                raise RuntimeError("hooked layers disagree on feature_upsample_res / head count")
-        out = ops.attn_map_rows([r.q for r in chosen], [r.k for r in chosen], heads, [r.scale for r in chosen], R, indices)
+        st = stack_of(chosen, "collect_maps_batched")
+        out = ops.attn_map_rows(st.qs, st.ks, st.heads, st.scales, st.R, indices)
     controller.reset()
     return out

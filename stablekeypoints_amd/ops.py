@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import weakref
+from collections import namedtuple
 from typing import List, Sequence, Tuple
 
 import torch
@@ -315,44 +316,6 @@ def _map_bwd_sparse(S, sides, B, H, T, R, sel, G, lse):
     return dS
 
 
-class AttnMapFn(torch.autograd.Function):
-    """M[b,t,:,:] = mean over (layer, head) of softmax_t(bicubic_R(scale * q_l k_l^T)).
-
-    Replaces ptp_utils.py:513-538 + optimize.py:27-79 (see csrc/skp_attn_map.hip).
-    apply(R, heads, scales(tuple), q_0, k_0, q_1, k_1, ...) with q_l [B,s_l^2,C_l], k_l [Bk,T,C_l].
-    """
-
-    @staticmethod
-    def forward(ctx, R: int, heads: int, scales: Tuple[float, ...], *qk: torch.Tensor):
-        L = len(qk) // 2
-        qs = [_dev(qk[2 * i], "q") for i in range(L)]
-        ks = [_dev(qk[2 * i + 1], "k") for i in range(L)]
-        B, T = qs[0].shape[0], ks[0].shape[1]
-        sides = []
-        for q in qs:
-            s = int(round(q.shape[1] ** 0.5))
-            if s * s != q.shape[1]:
-                raise RuntimeError("AttnMapFn: query length is not a square")
-            sides.append(s)
-        S = [qk_logits(q, k, heads, sc) for q, k, sc in zip(qs, ks, scales)]
-        M, lse = _map_fwd(S, sides, B, heads, T, R)
-        ctx.save_for_backward(lse, *qs, *ks, *S)
-        ctx.meta = (R, heads, tuple(scales), tuple(sides), B, T, L)
-        return M
-
-    @staticmethod
-    def backward(ctx, dM: torch.Tensor):
-        R, H, scales, sides, B, T, L = ctx.meta
-        saved = ctx.saved_tensors
-        lse, qs, ks, S = saved[0], saved[1:1 + L], saved[1 + L:1 + 2 * L], saved[1 + 2 * L:]
-        dM = _dev(dM, "dM")
-        # pad columns (t >= T) of a LAST partial group are written as 0 by the kernels; zero-fill covers the
-        # (never read) gap columns when T > 128 is not a multiple of 16
-        dS = [torch.empty_like(s_) if T <= TOKEN_GROUP else torch.zeros_like(s_) for s_ in S]
-        _map_bwd(S, dS, sides, B, H, T, R, dM, lse)
-        return (None, None, None, *_dqk_from_dS(qs, ks, dS, scales, H, T, ctx.needs_input_grad[3:]))
-
-
 def _dqk_from_dS(qs, ks, dS, scales, H: int, T: int, needs) -> List[torch.Tensor]:
     """dq_l = scale * dS_l k_l, dk_l = scale * dS_l^T q_l on the fp32-MFMA GEMM (deterministic; a shared k sums over the
     batch rows).  `needs[2l]`, `needs[2l+1]`: which gradients autograd asked for."""
@@ -378,12 +341,109 @@ def _dqk_from_dS(qs, ks, dS, scales, H: int, T: int, needs) -> List[torch.Tensor
     return grads
 
 
+class MapStack(namedtuple("MapStack", "qs ks heads scales R sides B Bk T L")):
+    """The hooked cross-attention layers behind one reduced map: q_l [B,s_l^2,C_l], k_l [Bk,T,C_l] with Bk in {1, B}, one head
+    count and up-res side R for all, one logit scale per layer; `sides` = (s_l), `Bk` = the context rows of layer 0.  Checked
+    here and nowhere else, before a kernel takes the geometry of layer 0 for every layer: shapes first (host tensors get that
+    far), then `_dev` on every tensor.  `who` names the caller in the errors."""
+    __slots__ = ()
+
+    def __new__(cls, who: str, qs, ks, heads: int, scales, R: int):
+        qs, ks, heads, scales = tuple(qs), tuple(ks), int(heads), tuple(float(v) for v in scales)
+        L = len(qs)
+        if L == 0 or len(ks) != L:
+            raise RuntimeError(f"{who}: empty layer stack: one q and one k per hooked layer, got {L} and {len(ks)}")
+        if len(scales) != L:
+            raise RuntimeError(f"{who}: one scale per layer: {len(scales)} scales for {L} layers")
+        B, Bk, T = qs[0].shape[0], ks[0].shape[0], ks[0].shape[1]
+        sides = []
+        for l, (q, k) in enumerate(zip(qs, ks)):
+            s = int(round(q.shape[1] ** 0.5))
+            bad = (f"query length {q.shape[1]} is not a square" if s * s != q.shape[1] else
+                   f"q has {q.shape[0]} batch rows, layer 0 has {B}" if q.shape[0] != B else
+                   f"k has {k.shape[0]} batch rows, neither 1 nor {B}" if k.shape[0] not in (1, B) else
+                   f"k has a token count of {k.shape[1]}, layer 0 has {T}" if k.shape[1] != T else
+                   f"{q.shape[2]} q channels do not split into {heads} heads" if q.shape[2] % heads else
+                   f"k has {k.shape[2]} channels, q has {q.shape[2]}" if k.shape[2] != q.shape[2] else None)
+            if bad:
+                raise RuntimeError(f"{who}: layer {l}: {bad}")
+            sides.append(s)
+        return super().__new__(cls, tuple(_dev(q, "q") for q in qs), tuple(_dev(k, "k") for k in ks), heads, scales, int(R),
+                               tuple(sides), B, Bk, T, L)
+
+    @classmethod
+    def of_flat(cls, who: str, qk, heads: int, scales, R: int):
+        """The stack of `flat()`'s (q_0, k_0, q_1, k_1, ...), as `Function.apply` hands it to a node's forward."""
+        return cls(who, qk[0::2], qk[1::2], heads, scales, R)
+
+    def flat(self):
+        return tuple(t for qk in zip(self.qs, self.ks) for t in qk)
+
+    def logits(self) -> List[torch.Tensor]:
+        return [qk_logits(q, k, self.heads, sc) for q, k, sc in zip(self.qs, self.ks, self.scales)]
+
+    def maps(self, tokrow=None, n_rows: int = 0):
+        """-> (S, M, lse): the layers' logits and `_map_fwd` of them."""
+        S = self.logits()
+        return (S, *_map_fwd(S, self.sides, self.B, self.heads, self.T, self.R, tokrow=tokrow, n_rows=n_rows))
+
+
+def _save_stack(ctx, st: MapStack, S, lse, *own):
+    """Keeps what a map node's backward needs: the tensors in autograd's saved-tensor slots, the geometry on `ctx`."""
+    ctx.save_for_backward(lse, *st.qs, *st.ks, *S, *own)
+    ctx.stack = st._replace(qs=(), ks=())
+
+
+def _saved_stack(ctx):
+    """-> (the stack, S, lse, own) that `_save_stack` kept."""
+    t, L = ctx.saved_tensors, ctx.stack.L
+    return ctx.stack._replace(qs=t[1:1 + L], ks=t[1 + L:1 + 2 * L]), t[1 + 2 * L:1 + 3 * L], t[0], t[1 + 3 * L:]
+
+
+def _stack_grads(st: MapStack, S, lse, needs, dM=None, rows=None, sparse=None):
+    """(dq_0, dk_0, dq_1, dk_1, ...) from the map gradient, given dense (`dM` [B,T,R,R]) or as its non-zero rows (`rows` =
+    (sel [B,K], G [B,K,R,R])).  Rows go to the sparse kernels where `sparse` says so -- None asks `map_bwd_sparse_supported` --
+    and are scattered into a dense gradient otherwise."""
+    B, H, T, R = st.B, st.heads, st.T, st.R
+    if rows is not None and sparse is None:
+        sparse = map_bwd_sparse_supported(st.sides, rows[0].shape[1], R, T, H)
+    if rows is not None and sparse:
+        dS = _map_bwd_sparse(S, st.sides, B, H, T, R, *rows, lse)
+    else:
+        if rows is not None:
+            sel, G = rows
+            dM = torch.zeros(B, T, R, R, device=G.device, dtype=torch.float32).scatter_(1, sel[:, :, None, None].expand_as(G), G)
+        # pad columns (t >= T) of a LAST partial group are written as 0 by the kernels; zero-fill covers the
+        # (never read) gap columns when T > 128 is not a multiple of 16
+        dS = [torch.empty_like(s_) if T <= TOKEN_GROUP else torch.zeros_like(s_) for s_ in S]
+        _map_bwd(S, dS, st.sides, B, H, T, R, _dev(dM, "dM"), lse)
+    return _dqk_from_dS(st.qs, st.ks, dS, st.scales, H, T, needs)
+
+
+class AttnMapFn(torch.autograd.Function):
+    """M[b,t,:,:] = mean over (layer, head) of softmax_t(bicubic_R(scale * q_l k_l^T)).
+
+    Replaces ptp_utils.py:513-538 + optimize.py:27-79 (see csrc/skp_attn_map.hip).
+    apply(R, heads, scales(tuple), q_0, k_0, q_1, k_1, ...) with q_l [B,s_l^2,C_l], k_l [Bk,T,C_l].
+    """
+
+    @staticmethod
+    def forward(ctx, R: int, heads: int, scales: Tuple[float, ...], *qk: torch.Tensor):
+        st = MapStack.of_flat("AttnMapFn", qk, heads, scales, R)
+        S, M, lse = st.maps()
+        _save_stack(ctx, st, S, lse)
+        return M
+
+    @staticmethod
+    def backward(ctx, dM: torch.Tensor):
+        st, S, lse, _ = _saved_stack(ctx)
+        return (None, None, None, *_stack_grads(st, S, lse, ctx.needs_input_grad[3:], dM=dM))
+
+
 def attn_map(qs: Sequence[torch.Tensor], ks: Sequence[torch.Tensor], heads: int, scales: Sequence[float],
              R: int) -> torch.Tensor:
-    flat = []
-    for q, k in zip(qs, ks):
-        flat += [q, k]
-    return AttnMapFn.apply(int(R), int(heads), tuple(float(s) for s in scales), *flat)
+    st = MapStack("attn_map", qs, ks, heads, scales, R)
+    return AttnMapFn.apply(st.R, st.heads, st.scales, *st.flat())
 
 
 @torch.no_grad()
@@ -392,35 +452,28 @@ def attn_map_rows(qs: Sequence[torch.Tensor], ks: Sequence[torch.Tensor], heads:
     """[B,len(indices),R,R]: the maps of the tokens `indices` only (optimize.py:58-59 `data[:, :, :, indices]`; inference
     keeps K of the T maps).  With a wide token axis (T > 128) the kernel writes just those rows -- the softmax still runs
     over all T tokens; otherwise all T maps are written and gathered.  No autograd (inference path)."""
-    T = ks[0].shape[1]
-    idx = torch.as_tensor(indices, device=qs[0].device).long().reshape(-1)
-    sides = [int(round(q.shape[1] ** 0.5)) for q in qs]
-    if any(s_ * s_ != q.shape[1] or q.shape[0] != qs[0].shape[0] or k.shape[1] != T for s_, q, k in zip(sides, qs, ks)):
-        raise RuntimeError("attn_map_rows: hooked layers disagree on batch rows / token count, or a query length is not a square")
-    S = [qk_logits(q.detach(), k.detach(), heads, sc) for q, k, sc in zip(qs, ks, scales)]
-    B = qs[0].shape[0]
-    if map_wide_supported(T, R, sides):
+    st = MapStack("attn_map_rows", qs, ks, heads, scales, R)
+    idx = torch.as_tensor(indices, device=st.qs[0].device).long().reshape(-1)
+    if map_wide_supported(st.T, st.R, st.sides):
         uniq, inv = torch.unique(idx, return_inverse=True)      # a token asked for twice is written once
-        tokrow = torch.full((T,), -1, device=idx.device, dtype=torch.int32)
+        tokrow = torch.full((st.T,), -1, device=idx.device, dtype=torch.int32)
         tokrow[uniq] = torch.arange(uniq.numel(), device=idx.device, dtype=torch.int32)
-        M, _ = _map_fwd(S, sides, B, heads, T, R, tokrow=tokrow, n_rows=int(uniq.numel()))
+        _, M, _ = st.maps(tokrow=tokrow, n_rows=int(uniq.numel()))
         return M if uniq.numel() == idx.numel() and bool((inv == torch.arange(idx.numel(), device=idx.device)).all()) else M[:, inv]
-    M, _ = _map_fwd(S, sides, B, heads, T, R)
-    return M[:, idx]
+    return st.maps()[1][:, idx]
 
 
 def materialize_probs(q: torch.Tensor, k: torch.Tensor, heads: int, scale: float, R: int) -> torch.Tensor:
     """Reference-layout tensor (B*h, R*R, T) of one hooked layer (ptp_utils.py:535-538), produced by
     the SAME fused kernel run one head at a time (L=1, H=1).  Compatibility/testing path only."""
-    B, T = q.shape[0], k.shape[1]
-    s = int(round(q.shape[1] ** 0.5))
-    S = qk_logits(q, k, heads, scale)
+    st = MapStack("materialize_probs", [q], [k], heads, [scale], R)
+    S, = st.logits()
     outs = []
     for h in range(heads):
         Sh = S[:, h:h + 1].contiguous()
-        Mh, _ = _map_fwd([Sh], [s], B, 1, T, R)               # [B,T,R,R]
-        outs.append(Mh.reshape(B, T, R * R).permute(0, 2, 1))
-    return torch.stack(outs, dim=1).reshape(B * heads, R * R, T)
+        Mh, _ = _map_fwd([Sh], st.sides, st.B, 1, st.T, R)      # [B,T,R,R]
+        outs.append(Mh.reshape(st.B, st.T, R * R).permute(0, 2, 1))
+    return torch.stack(outs, dim=1).reshape(st.B * heads, R * R, st.T)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -524,25 +577,15 @@ class MapLossesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, *qk: torch.Tensor):
-        L = len(qk) // 2
-        qs = [_dev(qk[2 * i], "q") for i in range(L)]
-        ks = [_dev(qk[2 * i + 1], "k") for i in range(L)]
-        R, H, scales = int(meta["R"]), int(meta["heads"]), tuple(float(v) for v in meta["scales"])
-        B, T = qs[0].shape[0], ks[0].shape[1]
+        st = MapStack.of_flat("MapLossesFn", qk, meta["heads"], meta["scales"], meta["R"])
+        R, B, T = st.R, st.B, st.T
         n = B // 2
         th_dev = meta.get("theta_inv_dev")          # [n, 6] float32 on the device, instead of meta["thetas"] (host numbers)
         if th_dev is not None and (not th_dev.is_cuda or th_dev.dtype != torch.float32 or tuple(th_dev.shape) != (n, 6) or not th_dev.is_contiguous()):
             raise RuntimeError("MapLossesFn: theta_inv_dev must be a contiguous float32 [n, 6] device tensor")
-        if B != 2 * n or len(scales) != L or (th_dev is None and len(meta["thetas"]) != n):
-            raise RuntimeError("MapLossesFn: rows must be n images followed by their n affine copies, one scale per layer")
-        sides = []
-        for q, k in zip(qs, ks):
-            s_ = int(round(q.shape[1] ** 0.5))
-            if s_ * s_ != q.shape[1] or q.shape[0] != B or k.shape[1] != T or q.shape[2] % H or k.shape[2] != q.shape[2]:
-                raise RuntimeError("MapLossesFn: hooked layers disagree on batch rows / token count / head split")
-            sides.append(s_)
-        S = [qk_logits(q, k, H, sc) for q, k, sc in zip(qs, ks, scales)]
-        M, lse = _map_fwd(S, sides, B, H, T, R)
+        if B != 2 * n or (th_dev is None and len(meta["thetas"]) != n):
+            raise RuntimeError("MapLossesFn: rows must be n images followed by their n affine copies, one affine per image")
+        S, M, lse = st.maps()
         sigma, ns = float(meta["sigma"]), int(meta["num_subjects"])
         n_cand = min(int(meta["n_cand"]), T)
         K = min(int(meta["top_k"]), n_cand)
@@ -590,23 +633,19 @@ class MapLossesFn(torch.autograd.Function):
             _launch("skp_losses_fwd_f32", M[i], M[n + i], sel_all[i], K, T, R, am, ns, sigma, th, partial[i], g_sharp[i],
                     g_eq_a[i], g_eq_b[i])
         sums = partial.sum(dim=(0, 2, 3)) / float(K * R * R)
-        ctx.save_for_backward(lse, sel_all, g_sharp, g_eq_a, g_eq_b, *qs, *ks, *S)
-        ctx.meta = (R, H, scales, tuple(sides), B, T, L)
+        _save_stack(ctx, st, S, lse, sel_all, g_sharp, g_eq_a, g_eq_b)
         ctx.mark_non_differentiable(sel_all)
         return sums[0], sums[1], sel_all
 
     @staticmethod
     def backward(ctx, go_sharp, go_equiv, _go_sel):
-        R, H, scales, sides, B, T, L = ctx.meta
-        saved = ctx.saved_tensors
-        lse, sel_all, g_sharp, g_eq_a, g_eq_b = saved[:5]
-        qs, ks, S = saved[5:5 + L], saved[5 + L:5 + 2 * L], saved[5 + 2 * L:]
+        st, S, lse, (sel_all, g_sharp, g_eq_a, g_eq_b) = _saved_stack(ctx)
         z = torch.zeros((), device=lse.device)
         gs = z if go_sharp is None else go_sharp.reshape(()).float()
         ge = z if go_equiv is None else go_equiv.reshape(()).float()
         G = torch.cat([gs * g_sharp + ge * g_eq_a, ge * g_eq_b], dim=0)            # [B,K,R,R]
-        dS = _map_bwd_sparse(S, sides, B, H, T, R, torch.cat([sel_all, sel_all], dim=0), G, lse)
-        return (None, *_dqk_from_dS(qs, ks, dS, scales, H, T, ctx.needs_input_grad[1:]))
+        rows = (torch.cat([sel_all, sel_all], dim=0), G)        # (the caller took this node because the sparse kernels serve it)
+        return (None, *_stack_grads(st, S, lse, ctx.needs_input_grad[1:], rows=rows, sparse=True))
 
 
 def point_loss(M, pos, sigma: float):
@@ -635,47 +674,25 @@ class MapPointLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, *qk: torch.Tensor):
-        L = len(qk) // 2
-        qs = [_dev(qk[2 * i], "q") for i in range(L)]
-        ks = [_dev(qk[2 * i + 1], "k") for i in range(L)]
-        R, H, scales = int(meta["R"]), int(meta["heads"]), tuple(float(v) for v in meta["scales"])
-        B, T = qs[0].shape[0], ks[0].shape[1]
+        st = MapStack.of_flat("MapPointLossFn", qk, meta["heads"], meta["scales"], meta["R"])
         sel, pos, tokrow = meta["sel"], meta["pos"], meta["tokrow"]
         K = sel.shape[0]
-        if len(scales) != L or tuple(pos.shape) != (B, K, 2) or tuple(tokrow.shape) != (T,):
-            raise RuntimeError("MapPointLossFn: one scale per layer, positions [B,K,2] and a row table of T tokens")
-        sides = []
-        for q, k in zip(qs, ks):
-            s_ = int(round(q.shape[1] ** 0.5))
-            if s_ * s_ != q.shape[1] or q.shape[0] != B or k.shape[1] != T or q.shape[2] % H or k.shape[2] != q.shape[2]:
-                raise RuntimeError("MapPointLossFn: hooked layers disagree on batch rows / token count / head split")
-            sides.append(s_)
-        S = [qk_logits(q, k, H, sc) for q, k, sc in zip(qs, ks, scales)]
-        if map_wide_supported(T, R, sides):
-            M, lse = _map_fwd(S, sides, B, H, T, R, tokrow=tokrow, n_rows=K)
+        if tuple(pos.shape) != (st.B, K, 2) or tuple(tokrow.shape) != (st.T,):
+            raise RuntimeError("MapPointLossFn: positions [B,K,2] and a row table of T tokens")
+        if map_wide_supported(st.T, st.R, st.sides):
+            S, M, lse = st.maps(tokrow=tokrow, n_rows=K)
         else:
-            M, lse = _map_fwd(S, sides, B, H, T, R)
+            S, M, lse = st.maps()
             M = M.index_select(1, sel)
         E, G = point_loss(M, pos, float(meta["sigma"]))
-        ctx.save_for_backward(lse, sel, G, *qs, *ks, *S)
-        ctx.meta = (R, H, scales, tuple(sides), B, T, L)
+        _save_stack(ctx, st, S, lse, sel, G)
         return E
 
     @staticmethod
     def backward(ctx, go):
-        R, H, scales, sides, B, T, L = ctx.meta
-        saved = ctx.saved_tensors
-        lse, sel, G = saved[:3]
-        qs, ks, S = saved[3:3 + L], saved[3 + L:3 + 2 * L], saved[3 + 2 * L:]
-        K = sel.shape[0]
-        G = go.reshape(B, 1, 1, 1).float() * G
-        if map_bwd_sparse_supported(sides, K, R, T, H):
-            dS = _map_bwd_sparse(S, sides, B, H, T, R, sel.expand(B, K), G, lse)
-        else:
-            dM = torch.zeros(B, T, R, R, device=G.device, dtype=torch.float32).index_copy_(1, sel, G)
-            dS = [torch.empty_like(s_) if T <= TOKEN_GROUP else torch.zeros_like(s_) for s_ in S]
-            _map_bwd(S, dS, sides, B, H, T, R, dM, lse)
-        return (None, *_dqk_from_dS(qs, ks, dS, scales, H, T, ctx.needs_input_grad[1:]))
+        st, S, lse, (sel, G) = _saved_stack(ctx)
+        rows = (sel.expand(st.B, sel.shape[0]), go.reshape(st.B, 1, 1, 1).float() * G)
+        return (None, *_stack_grads(st, S, lse, ctx.needs_input_grad[1:], rows=rows))
 
 
 UNWARP_MAX_K = 32
@@ -890,14 +907,10 @@ class GroupNormSiLUForkFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
-GN_FUSED_STATS = True
-GN_FORK = True
-
-
 def _blocks(x):
     """(block sums, blocks per image, pixels per block) that x's producing convolution left behind (`x._skp_blocks`, set by
     conv3x3_auto / conv3x3_s2 / conv3x3_small / conv3x3_gn_silu), or None when there are none or they do not describe x."""
-    blocks = getattr(x, "_skp_blocks", None) if GN_FUSED_STATS else None
+    blocks = getattr(x, "_skp_blocks", None)
     if blocks is not None and (blocks[0].shape[0] != x.shape[0] or blocks[0].shape[1] != x.shape[1]
                                or blocks[1] * blocks[2] != x.shape[2] * x.shape[3]):
         return None
@@ -912,8 +925,8 @@ def group_norm_silu(x, norm: torch.nn.GroupNorm, off=None, silu: bool = True):
 
 def group_norm_silu_fork(x, norm: torch.nn.GroupNorm, off=None, silu: bool = True):
     """(group_norm_silu(x), x') with x' = x for the block's residual path: see GroupNormSiLUForkFn.  Without a gradient to
-    carry (or with the switch off) x' is x itself and nothing changes."""
-    if not (GN_FORK and torch.is_grad_enabled() and x.requires_grad):
+    carry x' is x itself and nothing changes."""
+    if not (torch.is_grad_enabled() and x.requires_grad):
         return group_norm_silu(x, norm, off=off, silu=silu), x
     return GroupNormSiLUForkFn.apply(x, off, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, _blocks(x))
 
@@ -1095,11 +1108,8 @@ def add_bias_residual(a, b, bias):
 # ---------------------------------------------------------------------------------------------------------
 # residual add + LayerNorm of the transformer blocks, one pass per direction (csrc/skp_layer_norm.hip)
 # ---------------------------------------------------------------------------------------------------------
-ADD_LN = True
-
-
 def add_layer_norm_supported(h, norm: torch.nn.LayerNorm) -> bool:
-    return bool(ADD_LN and h.is_cuda and h.dtype == torch.float32 and len(norm.normalized_shape) == 1
+    return bool(h.is_cuda and h.dtype == torch.float32 and len(norm.normalized_shape) == 1
                 and norm.elementwise_affine and norm.bias is not None and h.shape[-1] == norm.normalized_shape[0]
                 and not (norm.weight.requires_grad or norm.bias.requires_grad)
                 and N.lib().skp_add_layer_norm_ok(int(h.shape[-1])))
@@ -1282,7 +1292,7 @@ def conv3x3_wanted(x_shape, w_shape):
 
 def conv3x3_stats_blocks(x_shape, w_shape) -> int:
     """256-pixel blocks per image if the forward convolution of this shape can leave output statistics behind, else 0."""
-    if not (GN_FUSED_STATS and conv3x3_f4_ok(x_shape, w_shape)):
+    if not conv3x3_f4_ok(x_shape, w_shape):
         return 0
     b, ci, h, w = (int(v) for v in x_shape)
     co = int(w_shape[0])
@@ -1390,15 +1400,12 @@ def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
 
 
 # GroupNorm(+offset)+SiLU folded into the consuming Winograd convolution (forward only, single output-channel group):
-# saves the norm's apply pass (one read + one write of the activation); GN_FOLD = False for A/B runs.
-GN_FOLD = True
-
-
+# saves the norm's apply pass (one read + one write of the activation).
 def conv3x3_gn_fold_ok(x, norm: torch.nn.GroupNorm, weight, *others) -> bool:
     """`others`: every further tensor the folded call will read (offset, bias, residual).  The folded kernel is forward
     only: with autograd on, ANY operand that requires a gradient (input, norm affine, weight, offset, bias, residual) sends
     the block down the differentiable route."""
-    if not (GN_FOLD and x.is_cuda and x.dtype == torch.float32):
+    if not (x.is_cuda and x.dtype == torch.float32):
         return False
     if torch.is_grad_enabled() and any(t_ is not None and t_.requires_grad
                                        for t_ in (x, weight, norm.weight, norm.bias, *others)):
@@ -1462,7 +1469,7 @@ def conv3x3_small(x, weight, bias=None, want_stats=False):
     B, ci, H, W = x.shape
     y = torch.empty(B, w.shape[0], H, W, device=x.device, dtype=torch.float32)
     bb = _dev(bias.detach(), "bias") if bias is not None else None
-    nblk = int(N.lib().skp_conv3x3_small_stats_blocks(B, ci, w.shape[0], H, W)) if (want_stats and GN_FUSED_STATS) else 0
+    nblk = int(N.lib().skp_conv3x3_small_stats_blocks(B, ci, w.shape[0], H, W)) if want_stats else 0
     if nblk:
         stats = torch.empty(B, w.shape[0], nblk, 2, device=x.device, dtype=torch.float32)
         _launch("skp_conv3x3_small_stats_f32", x, w, bb, y, stats, B, ci, w.shape[0], H, W)
@@ -1753,16 +1760,13 @@ def weight_stack(ws):
     return cached(ws[0], ("stack", *map(id, ws)), ws, lambda: torch.stack([w.detach() for w in ws]).contiguous())
 
 
-QKV_STACKED = True   # one batched GEMM with a broadcast A operand
-
-
 def _qkv_forward(x, wq, wk, wv):
     """q, k, v as ONE strided-batched GEMM: A = x with batch stride 0, B_i = W_i^T, C = [3, M, C] -- three times the
     workgroups of a single projection in one launch and three contiguous outputs (no strided views for the attention
     kernels).  Bit-equal to three F.linear calls per library kernel choice; 8 rows: 220 -> 180 us at 64^2, 186 -> 165 us
     at 16^2, 2 rows: 79 -> 49 us (tools/qkv_probe.py)."""
     F = torch.nn.functional
-    if not (QKV_STACKED and x.is_cuda and wq.shape == wk.shape == wv.shape):
+    if not (x.is_cuda and wq.shape == wk.shape == wv.shape):
         return F.linear(x, wq), F.linear(x, wk), F.linear(x, wv)
     c_in, c_out = wq.shape[1], wq.shape[0]
     x2 = x.reshape(-1, c_in)
@@ -1792,13 +1796,10 @@ class QKVProjFn(torch.autograd.Function):
         return dx.reshape(*shp[:-1], wq.shape[1]), None, None, None
 
 
-QKV_ACCUM = True
-
-
 def qkv_proj(x, wq, wk, wv):
     """Self-attention projections; frozen bias-free weights take the accumulate-in-GEMM backward."""
     frozen = not (wq.requires_grad or wk.requires_grad or wv.requires_grad)
-    if QKV_ACCUM and x.is_cuda and x.requires_grad and torch.is_grad_enabled() and frozen:
+    if x.is_cuda and x.requires_grad and torch.is_grad_enabled() and frozen:
         return QKVProjFn.apply(x, wq, wk, wv)
     if frozen and not (x.requires_grad and torch.is_grad_enabled()):
         return _qkv_forward(x, wq, wk, wv)
@@ -1844,7 +1845,7 @@ def self_attention_block(x, wq, wk, wv, heads: int, scale: float):
     the fused input gradient where the kernels serve the head size; the composition of `qkv_proj` and `self_attention`
     otherwise (no gradient wanted, other head sizes)."""
     frozen = not (wq.requires_grad or wk.requires_grad or wv.requires_grad)
-    if (QKV_STACKED and QKV_ACCUM and x.is_cuda and x.dim() == 3 and frozen and x.requires_grad
+    if (x.is_cuda and x.dim() == 3 and frozen and x.requires_grad
             and torch.is_grad_enabled() and wq.shape == wk.shape == wv.shape and wq.shape[0] % heads == 0
             and (wq.shape[0] // heads) in FA2_HEAD_DIMS):
         routes.note("attn.self", "fused_qkv")
@@ -1882,9 +1883,6 @@ def conv3x3_s2_tile_only(x, weight) -> bool:
     return (h, w) != tuple(x.shape[2:]) and conv3x3_s2_supported(x[:, :, :1, :1].expand(-1, -1, h, w), weight)
 
 
-S2_BWD_OWN = True
-
-
 class ConvS2Fn(torch.autograd.Function):
     """Stride-2 3x3 convolution of a frozen UNet Downsample2D whose INPUT needs a gradient: forward on the direct MFMA
     kernel.  Input gradient: the transposed stride-2 convolution is the stride-1 convolution of the ZERO-STUFFED output
@@ -1905,7 +1903,7 @@ class ConvS2Fn(torch.autograd.Function):
         w = ctx.weight
         b, c, h, wd = ctx.xshape
         co = w.shape[0]
-        if S2_BWD_OWN and h % 2 == 0 and wd % 2 == 0 and conv3x3_wanted((b, co, h, wd), (c, co, 3, 3)):
+        if h % 2 == 0 and wd % 2 == 0 and conv3x3_wanted((b, co, h, wd), (c, co, 3, 3)):
             dy = _dev(dy, "dy")
             routes.note("conv3x3_s2.bwd_data", "zero_stuffed")
             up = torch.zeros(b, co, h, wd, device=dy.device, dtype=torch.float32)
@@ -1938,7 +1936,7 @@ def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
         routes.note("conv3x3_s2", "s2_wino")
         U = _filters(weight, "s2w")
         nblk = (H // 8) * (W // 8) // 16
-        if want_stats and GN_FUSED_STATS and nblk * 16 == (H // 8) * (W // 8):
+        if want_stats and nblk * 16 == (H // 8) * (W // 8):
             stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
             _launch("skp_conv3x3_s2w_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))
             y._skp_blocks = (stats, nblk, 256)
@@ -1947,7 +1945,7 @@ def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
         return y
     routes.note("conv3x3_s2", "s2_direct")
     U = _filters(weight, "s2")
-    if want_stats and GN_FUSED_STATS:
+    if want_stats:
         nblk = (H // 16) * (W // 32)
         stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
         _launch("skp_conv3x3_s2_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))

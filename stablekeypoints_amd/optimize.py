@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from . import dist as skp_dist
 from . import ops, ptp_utils
 from . import routes as _routes
-from ._maps import collect_maps, collect_maps_batched          # noqa: F401  (collect_maps is public API)
+from ._maps import collect_maps, collect_maps_batched, stack_of          # noqa: F401  (collect_maps is public API)
 from .eval import find_k_max_pixels
 from .invertable_transform import RandomAffineWithInverse
 from .optimize_token import gaussian_circles
@@ -213,25 +213,21 @@ def _group_losses(controller, thetas, args, n, theta_inv_dev=None):
     row -- taken where it is the faster one (T > 128 by default, see ops.MAP_BWD_MODE).  Otherwise the general route:
     maps as a tensor, one loss node per image, dense [2n,T,R,R] map gradient."""
     records = [rec for i, rec in enumerate(controller.step_store["attn"]) if i in args.layers]
-    sides = [int(round(r.q.shape[1] ** 0.5)) for r in records]
-    T = records[0].k.shape[1]
-    n_cand = min(args.furthest_point_num_samples, T)
+    st = stack_of(records, "_group_losses")
+    n_cand = min(args.furthest_point_num_samples, st.T)
     K = min(args.top_k, n_cand)
-    fused = ops.map_bwd_sparse_supported(sides, K, records[0].R, T, records[0].heads) and K >= 2
+    fused = ops.map_bwd_sparse_supported(st.sides, K, st.R, st.T, st.heads) and K >= 2
     controller.fused_route = bool(fused)                          # GraphedStep captures only steps that take the fused node
     if theta_inv_dev is not None and not fused:
         raise RuntimeError("_group_losses: device-resident affines are served by the fused map + losses node only")
     if fused:
-        meta = dict(R=records[0].R, heads=records[0].heads, scales=[r.scale for r in records],
+        meta = dict(R=st.R, heads=st.heads, scales=st.scales,
                     thetas=None if theta_inv_dev is not None else [thetas[i].reshape(-1).tolist() for i in range(n)],
                     theta_inv_dev=theta_inv_dev, sigma=args.sigma,
                     num_subjects=getattr(args, "num_subjects", 1), strategy=getattr(args, "top_k_strategy", "gaussian"),
                     n_cand=n_cand, top_k=K, score_fn=token_order)
-        flat = []
-        for r in records:
-            flat += [r.q, r.k]
         controller.reset()
-        tot_s, tot_e, _ = ops.MapLossesFn.apply(meta, *flat)
+        tot_s, tot_e, _ = ops.MapLossesFn.apply(meta, *st.flat())
         return tot_e, tot_s
     maps = collect_maps_batched(controller, layers=args.layers)  # [2n,T,R,R]
     dev = maps.device

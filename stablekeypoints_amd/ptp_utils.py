@@ -32,7 +32,7 @@ from . import ops
 from . import routes
 from .ldm.samplers import SamplerPlan, step_formula
 from .ldm.unet import StopForward
-from ._maps import FusedAttn, _materialize_host, collect_maps
+from ._maps import FusedAttn, _materialize_host, collect_maps, stack_of
 
 
 # ---------------------------------------------------------------------------------------------
@@ -526,18 +526,18 @@ def _energy_grad(model, latents, context, t, targets, sigma, layers=(0, 1, 2, 3)
         if not chosen or not all(isinstance(r, FusedAttn) for r in chosen):
             raise RuntimeError("keypoint_energy_grad: no stored attention layer matches `layers` (or the store materialises its "
                                "entries: AttentionStore(materialize=True) keeps no autograd history)")
-        R, heads = chosen[0].R, chosen[0].heads
-        qs = [r.q[-n:] for r in chosen]                                       # the conditional rows are the last n of the forward
-        ks = [r.k if r.k.shape[0] == 1 else r.k[-n:] for r in chosen]
         if x.is_cuda and x.dtype == torch.float32:
             routes.note("sample.keypoints", "map_point_loss")
-            meta = dict(R=R, heads=heads, scales=[r.scale for r in chosen], sigma=float(sigma), pos=pos, sel=sel, tokrow=tokrow)
-            E = ops.MapPointLossFn.apply(meta, *[v for q, k in zip(qs, ks) for v in (q, k)])
+            st = stack_of(chosen, "keypoint_energy_grad", rows=slice(-n, None))   # the conditional rows: the last n of the forward
+            meta = dict(R=st.R, heads=st.heads, scales=st.scales, sigma=float(sigma), pos=pos, sel=sel, tokrow=tokrow)
+            E = ops.MapPointLossFn.apply(meta, *st.flat())
         else:
             routes.note("sample.keypoints", "host")
+            R, heads = chosen[0].R, chosen[0].heads
             M = 0
-            for r, q, k in zip(chosen, qs, ks):
-                probs = _materialize_host(q, k, heads, r.scale, R)            # (n * heads, R^2, T)
+            for r in chosen:
+                k = r.k if r.k.shape[0] == 1 else r.k[-n:]
+                probs = _materialize_host(r.q[-n:], k, heads, r.scale, R)     # (n * heads, R^2, T)
                 M = M + probs.reshape(n, heads, R * R, -1)[..., ids].mean(dim=1)
             M = (M / len(chosen)).permute(0, 2, 1).reshape(n, len(ids), R, R)
             p = pos.to(M.dtype) * R
