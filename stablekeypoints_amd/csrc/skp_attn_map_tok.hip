@@ -251,7 +251,6 @@ __global__ __launch_bounds__(512, (SM <= 16 ? 2 : 1)) void skp_map_bwd_tok_kerne
     float* __restrict__ outp = ly.out + (size_t)(b * a.H + hA) * ly.out_bh + (size_t)m * ly.out_band + t;
     int cur = skp_tap_i0(rs_tab, y0);                          // dz window rows: cur-1 .. cur+2
     const int rlo = cur - 1 < 0 ? 0 : cur - 1;                 // first row this band emits (partials are band-relative)
-    const float keep = live ? 1.f : 0.f;
     const int sbase = ((b * a.H + hA) * s * s) * a.ldt * 4 + t * 4;        // byte offset of S[b,h,0,t]
     const int col_bytes = a.ldt * 4;
 
@@ -262,17 +261,20 @@ __global__ __launch_bounds__(512, (SM <= 16 ? 2 : 1)) void skp_map_bwd_tok_kerne
             float* o = outp + (size_t)(a.NB == 1 ? idx : idx - rlo) * ly.out_row;
 #pragma unroll
             for (int c = 0; c < SM; ++c)
-                if (c < s) o[(size_t)c * ly.out_col] = row[c] * keep;
+                if (c < s) o[(size_t)c * ly.out_col] = live ? row[c] : 0.f;   // (a pad token's 0 logit can overflow against a low lse)
         }
     };
 
     for (int y = y0; y < y1;) {
         const TapS tya = skp_tap(rs_tab, y);
         const int ty_i0 = skp_tap_i0(rs_tab, y);
-        // the partner row: the next one when it reads the same four source rows, else a copy of this row with zero weight
+        // the partner row: the next one when it reads the same four source rows, else a copy of this row with zero weight in
+        // the adjoint.  The copy interpolates with this row's taps (tyv), so its probabilities are this row's and finite: with
+        // zero taps its logits would be 0, and 2^(0 - lse) overflows once every real logit sits below -128.
         const bool pair = y + 1 < y1 && skp_tap_i0(rs_tab, y + 1) == ty_i0;
         const int yb = pair ? y + 1 : y;
-        TapS tyb = skp_tap(rs_tab, yb);
+        const TapS tyv = skp_tap(rs_tab, yb);
+        TapS tyb = tyv;
         if (!pair) tyb = TapS{0.f, 0.f, 0.f, 0.f};
         while (cur < ty_i0) {                                  // slot 0 is complete for this band
             if (cur - 1 < 0) win1 += win0;                     // clamped row: belongs to the border row
@@ -302,11 +304,11 @@ __global__ __launch_bounds__(512, (SM <= 16 ? 2 : 1)) void skp_map_bwd_tok_kerne
         int ccur = skp_tap_i0(rs_tab, 0);
         float raw[4], raw1[4], raw2[4], vwa[4], vwb[4], acca[4] = {0.f, 0.f, 0.f, 0.f}, accb[4] = {0.f, 0.f, 0.f, 0.f};
         vcol_load(ccur - 1, raw); vcol_load(ccur, raw1); vcol_load(ccur + 1, raw2);
-        vwa[0] = vcol(raw, tya); vwb[0] = vcol(raw, tyb);
-        vwa[1] = vcol(raw1, tya); vwb[1] = vcol(raw1, tyb);
-        vwa[2] = vcol(raw2, tya); vwb[2] = vcol(raw2, tyb);
+        vwa[0] = vcol(raw, tya); vwb[0] = vcol(raw, tyv);
+        vwa[1] = vcol(raw1, tya); vwb[1] = vcol(raw1, tyv);
+        vwa[2] = vcol(raw2, tya); vwb[2] = vcol(raw2, tyv);
         vcol_load(ccur + 2, raw);
-        vwa[3] = vcol(raw, tya); vwb[3] = vcol(raw, tyb);
+        vwa[3] = vcol(raw, tya); vwb[3] = vcol(raw, tyv);
         vcol_load(ccur + 3, raw);                              // the columns the next two window positions add
         vcol_load(ccur + 4, raw1);
         const f32x2* __restrict__ ldra = ldp + (size_t)y * R;
@@ -343,7 +345,7 @@ __global__ __launch_bounds__(512, (SM <= 16 ? 2 : 1)) void skp_map_bwd_tok_kerne
                         acca[0] = acca[1]; acca[1] = acca[2]; acca[2] = acca[3]; acca[3] = 0.f;
                         accb[0] = accb[1]; accb[1] = accb[2]; accb[2] = accb[3]; accb[3] = 0.f;
                         vwa[0] = vwa[1]; vwa[1] = vwa[2]; vwa[2] = vwa[3]; vwa[3] = vcol(raw, tya);
-                        vwb[0] = vwb[1]; vwb[1] = vwb[2]; vwb[2] = vwb[3]; vwb[3] = vcol(raw, tyb);
+                        vwb[0] = vwb[1]; vwb[1] = vwb[2]; vwb[2] = vwb[3]; vwb[3] = vcol(raw, tyv);
                         ++ccur;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) raw[q] = raw1[q];
