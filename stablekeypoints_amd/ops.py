@@ -908,8 +908,8 @@ class GroupNormSiLUForkFn(torch.autograd.Function):
 
 
 def _blocks(x):
-    """(block sums, blocks per image, pixels per block) that x's producing convolution left behind (`x._skp_blocks`, set by
-    conv3x3_auto / conv3x3_s2 / conv3x3_small / conv3x3_gn_silu), or None when there are none or they do not describe x."""
+    """(block sums, blocks per image, pixels per block) that x's producing convolution left behind (`x._skp_blocks`, written by
+    `_leave_blocks` alone), or None when there are none or they do not describe x."""
     blocks = getattr(x, "_skp_blocks", None)
     if blocks is not None and (blocks[0].shape[0] != x.shape[0] or blocks[0].shape[1] != x.shape[1]
                                or blocks[1] * blocks[2] != x.shape[2] * x.shape[3]):
@@ -1242,6 +1242,7 @@ def _conv3x3_f4r_raw(x, R, bias, cout, residual=None, out=None):
 
 
 def conv3x3_f4r_ok(x_shape, cout) -> bool:
+    """The raw-filter gate (the one statement `conv3x3_plan` consults, at most once per plan)."""
     b, ci, h, w = (int(v) for v in x_shape)
     return CONV3X3_MODE == "f4" and bool(N.lib().skp_conv3x3_f4r_ok(b, ci, int(cout), h, w))
 
@@ -1249,26 +1250,13 @@ def conv3x3_f4r_ok(x_shape, cout) -> bool:
 # "f4": Winograd F(4x4,3x3) where the shape allows (H, W % 4 == 0), F(2x2,3x3) otherwise; "f2": F(2x2,3x3) only;
 # "lib": library convolution everywhere (A/B runs and the consistency test).  Default f4.
 CONV3X3_MODE = "f4"
-
-
-def conv3x3_f4_ok(x_shape, w_shape):
-    """F(4x4,3x3) serves the launch: >= 32 tiles (one tile block of the transformed-filter kernels), or fewer on the
-    raw-filter form where it is routed (>= 1280 channels on both sides: the 8^2 layers of a 1- or 2-row step -- config 3's
-    per-rank shape -- ran on the library at 120 us per call incl. its layout transposes; the raw-filter kernel takes the
-    same 55 us as at 8 rows, its idle tile lanes cost nothing extra)."""
-    b, _, h, w = (int(v) for v in x_shape)
-    if not (CONV3X3_MODE == "f4" and h % 4 == 0 and w % 4 == 0 and int(w_shape[0]) % 16 == 0 and int(w_shape[1]) % 16 == 0
-            and 36 * int(w_shape[0]) * int(w_shape[1]) * 4 < 2 ** 31):
-        return False
-    return b * (h // 4) * (w // 4) >= 32 or conv3x3_f4r_ok(x_shape, int(w_shape[0]))
-
-
+GN_ONEPASS = True        # False (tests): producers leave block statistics behind even where the norm would not want them
 _CONV3X3_OWN_ONLY = False
 
 
 @contextlib.contextmanager
 def conv3x3_own_kernels():
-    """Inside the block `conv3x3_wanted` drops its tile-count rule: every shape the Winograd kernels can run takes them.  The VAE
+    """Inside the block `conv3x3_plan` drops its tile-count rule: every shape the Winograd kernels can run takes them.  The VAE
     decoder runs in it (ldm/fused.py): a one-image latency path, whose full-width launches pass the tile rule anyway (one 64^2
     latent is 256 tiles) -- only reduced-width trees at 8^2 differ, and those then stay on the HIP kernels instead of the library."""
     global _CONV3X3_OWN_ONLY
@@ -1279,67 +1267,128 @@ def conv3x3_own_kernels():
         _CONV3X3_OWN_ONLY = prev
 
 
-def conv3x3_wanted(x_shape, w_shape):
-    """Supported AND enough tiles to fill the MFMA column blocks (layers with few workgroups are split over input
-    channels inside the library call, so the channel counts do not matter here)."""
-    if CONV3X3_MODE == "lib" or not conv3x3_supported(x_shape, w_shape):
-        return False
-    if _CONV3X3_OWN_ONLY:
-        return True
-    b, _, h, w = (int(v) for v in x_shape)
-    return conv3x3_f4_ok(x_shape, w_shape) or b * ((h + 1) // 2) * ((w + 1) // 2) >= 128
-
-
-def conv3x3_stats_blocks(x_shape, w_shape) -> int:
-    """256-pixel blocks per image if the forward convolution of this shape can leave output statistics behind, else 0."""
-    if not conv3x3_f4_ok(x_shape, w_shape):
-        return 0
-    b, ci, h, w = (int(v) for v in x_shape)
-    co = int(w_shape[0])
-    if max(ci, co) * h * w * 4 * b >= 2 ** 31:           # chunked launches: keep the plain path
-        return 0
-    return int(N.lib().skp_conv3x3_f4_stats_blocks(b, ci, co, h, w))
-
-
 def _rows_per_launch(ci, co, H, W) -> int:
     """Batch rows one convolution launch takes under the kernels' 32-bit byte offsets (< 2 GiB per tensor)."""
     return max(1, (2 ** 31 - 1) // (max(ci, co) * H * W * 4))
 
 
-def _conv3x3_run(x, weight, backward, bias, residual, cout, stats=None):
-    w_shape = (weight.shape[1], weight.shape[0], 3, 3) if backward else weight.shape
-    f4 = conv3x3_f4_ok(x.shape, w_shape)
-    B, ci, H, W = x.shape
+# One stride-1 3x3 launch, decided: `site` / `route` = the ledger entry ("lib": the kernels are not wanted), `form` = the filter
+# layout (a key of _FILTER_FORMS) and with it the kernel family, `rows` = batch rows per launch, `nblk` / `pixels` = statistics
+# blocks per image the launch leaves behind (0: none) and pixels per block, `fold` = a GroupNorm fold was asked for and the
+# folded kernel serves every chunk, the tail included.
+ConvPlan = namedtuple("ConvPlan", "site route form rows nblk pixels fold")
+
+
+def conv3x3_plan(x_shape, w_shape, *, backward=False, want_stats=False, gn_fold=None, forced=False) -> ConvPlan:
+    """Every decision about the 3x3 / stride 1 / pad 1 convolution of x [B,Cin,H,W] with a filter of shape `w_shape` [Cout,Cin,3,3]
+    (backward-data: x = dy, channel roles already swapped), from the shapes and the module switches alone: pure host code, each
+    library query asked at most once and only where its answer can matter, nothing kept between calls (skp_tune_set and the
+    switches change the answers).  `want_stats`: True = for the GroupNorm that follows, "always" = whatever follows (callers that
+    read the blocks themselves); `gn_fold`: the groups of a GroupNorm(+SiLU) to apply in the patch load; `forced`: ops.conv3x3."""
     site = "conv3x3.bwd_data" if backward else "conv3x3"
-    if f4 and stats is None and conv3x3_f4r_ok(x.shape, cout):          # small spatial size, many channels: raw-filter form
-        routes.note(site, "wino4_raw")
-        return _conv3x3_f4r_raw(x, _filters(weight, "f4r", backward), bias, cout, residual=residual)
-    U = _filters(weight, "f4" if f4 else "f2", backward)
-    run = _conv3x3_f4_raw if f4 else _conv3x3_raw
-    chunk = _rows_per_launch(ci, cout, H, W)
-    routes.note(site, routes.wino4_form(cout, min(B, chunk), H, W) if f4 else "wino2")
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        return ConvPlan(site, "lib", None, 0, 0, 256, False)
+    (b, xci, h, w), co, ci, lib = (int(v) for v in x_shape), int(w_shape[0]), int(w_shape[1]), N.lib()
+    rows = min(b, _rows_per_launch(xci, co, h, w))
+    # F(4x4) serves: >= 32 tiles (one tile block of the transformed-filter kernels), or fewer on the raw-filter form where the
+    # library routes it (>= 1280 channels on both sides: the 8^2 layers of a 1- or 2-row step -- config 3's per-rank shape -- ran on
+    # the library at 120 us per call incl. its layout transposes; the raw-filter kernel takes the same 55 us as at 8 rows)
+    f4 = CONV3X3_MODE == "f4" and h % 4 == 0 and w % 4 == 0 and co % 16 == 0 and ci % 16 == 0 and 36 * co * ci * 4 < 2 ** 31
+    raw = None
+    if f4 and b * (h // 4) * (w // 4) < 32:
+        f4 = raw = conv3x3_f4r_ok(x_shape, co)
+    # wanted: supported AND enough tiles to fill the MFMA column blocks (layers with few workgroups are split over input channels
+    # inside the library call, so the channel counts do not matter here); own kernels only / forced: no tile rule
+    supported = conv3x3_supported(x_shape, w_shape)
+    wanted = supported and (forced or (CONV3X3_MODE != "lib" and (_CONV3X3_OWN_ONLY or f4 or b * ((h + 1) // 2) * ((w + 1) // 2) >= 128)))
+    nblk, fold = 0, False
+    if f4 and supported and not backward:
+        if gn_fold is not None:      # the norm's kernels take x, and the folded kernel takes the full chunks and the tail chunk
+            fold = (xci % gn_fold == 0 and (h * w) % 4 == 0 and b * gn_fold <= 65535 and bool(lib.skp_conv3x3_f4_gn_ok(rows, xci, co, h, w))
+                    and (b % rows == 0 or bool(lib.skp_conv3x3_f4_gn_ok(b % rows, xci, co, h, w))))
+        # statistics: one launch for the whole batch, and only where the GroupNorm that follows does not hold its rows in registers
+        # anyway (the one-pass form computes exact statistics from the row it has loaded; the library says which)
+        if want_stats and rows == b and (want_stats == "always" or not (
+                GN_ONEPASS and co % 32 == 0 and lib.skp_group_norm_onepass_ok(1, co, 32, h * w))):
+            nblk = int(lib.skp_conv3x3_f4_stats_blocks(b, xci, co, h, w))
+    # the raw-filter form leaves no statistics and folds no norm; asked (if not above) only of a plain launch that will run: a plan
+    # made with `gn_fold` is about the folded launch alone, and no caller runs it without its `fold`
+    raw = f4 and not (nblk or fold) and (raw if raw is not None else wanted and gn_fold is None and conv3x3_f4r_ok(x_shape, co))
+    form = "f4r" if raw else "f4" if f4 else "f2"
+    # (a batch launched in chunks is named by its full chunks)
+    route = "lib" if not wanted else "wino4_raw" if form == "f4r" else routes.wino4_form(co, rows, h, w) if f4 else "wino2"
+    return ConvPlan(site, route, form, rows, nblk, 256, fold)
+
+
+# the earlier predicates, as views of the plan (bench.py, tools/, ldm/fused.py and the tests ask them)
+def conv3x3_f4_ok(x_shape, w_shape):
+    return conv3x3_plan(x_shape, w_shape).form in ("f4", "f4r")
+
+
+def conv3x3_wanted(x_shape, w_shape):
+    return conv3x3_plan(x_shape, w_shape).route != "lib"
+
+
+def conv3x3_stats_blocks(x_shape, w_shape) -> int:
+    """256-pixel blocks per image if the forward convolution of this shape can leave output statistics behind, else 0."""
+    return conv3x3_plan(x_shape, w_shape, want_stats="always").nblk
+
+
+def _leave_blocks(y, stats, nblk, pixels):
+    """The one writer of `y._skp_blocks` = (block sums [B,C,nblk,2], blocks per image, pixels per block), which `_blocks` reads for
+    the norm that consumes y (the same tensor object only).  -> y"""
     if stats is not None:
-        return _conv3x3_f4_raw(x, U, bias, cout, residual=residual, stats=stats)
-    if B <= chunk:
-        return run(x, U, bias, cout, residual=residual)
+        y._skp_blocks = (stats, nblk, pixels)
+    return y
+
+
+def _rows(t, b0, b1):
+    """Rows b0..b1 of t; t itself where that is all of it (the one-launch path makes no views)."""
+    return t if t is None or (b0 == 0 and b1 == t.shape[0]) else t[b0:b1]
+
+
+def _conv3x3_run(who, x, weight, bias, residual, plan: ConvPlan, stats=None, fold=None):
+    """Executes `plan` (of `conv3x3_plan` for these operands): one ledger note, one filter, one loop over the batch chunks.
+    `stats` [B,Cout,plan.nblk,2]: the launch leaves its block sums there; `fold` = (GroupNorm, offset or None): the folded kernel.
+    What the plan does not serve is refused here, before anything is launched."""
+    backward = plan.site == "conv3x3.bwd_data"
+    B, ci, H, W = x.shape
+    cout = int(weight.shape[1] if backward else weight.shape[0])
+    bad = (f"the Winograd kernels are not planned for x {tuple(x.shape)}, weight {tuple(weight.shape)}" if plan.route == "lib" else
+           f"block statistics on a plan of form {plan.form} that leaves none" if stats is not None and not (plan.form == "f4" and plan.nblk) else
+           f"statistics of shape {tuple(stats.shape)}, the plan leaves {(B, cout, plan.nblk, 2)}"
+           if stats is not None and tuple(stats.shape) != (B, cout, plan.nblk, 2) else
+           f"residual of shape {tuple(residual.shape)}, the output has {(B, cout, H, W)}"
+           if residual is not None and tuple(residual.shape) != (B, cout, H, W) else
+           "the folded kernel does not serve this launch (ask conv3x3_gn_fold_ok first)" if fold is not None and not plan.fold else None)
+    if bad:
+        raise RuntimeError(f"{who}: {bad}")
+    routes.note(plan.site, plan.route)
+    coef = _gn_fold_coef(x, *fold) if fold is not None else None
+    U = _filters(weight, plan.form, backward)
     y = torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
-    for b0 in range(0, B, chunk):
-        b1 = min(B, b0 + chunk)
-        run(x[b0:b1], U, bias, cout, residual=None if residual is None else residual[b0:b1], out=y[b0:b1])
+    for b0 in range(0, B, plan.rows):
+        b1 = min(B, b0 + plan.rows)
+        xs, rs, ys = _rows(x, b0, b1), _rows(residual, b0, b1), _rows(y, b0, b1)
+        if coef is not None:
+            _launch("skp_conv3x3_f4_gn_f32", xs, U, bias, rs, ys, _rows(stats, b0, b1), coef[b0:b1], b1 - b0, ci, cout, H, W)
+        elif plan.form == "f4r":                         # small spatial size, many channels: raw-filter form
+            _conv3x3_f4r_raw(xs, U, bias, cout, residual=rs, out=ys)
+        elif plan.form == "f4":
+            _conv3x3_f4_raw(xs, U, bias, cout, residual=rs, out=ys, stats=stats)
+        else:
+            _conv3x3_raw(xs, U, bias, cout, residual=rs, out=ys)
     return y
 
 
 class Conv3x3Fn(torch.autograd.Function):
-    """y = conv2d(x, weight, bias, stride 1, padding 1) (+ residual) with frozen weight/bias; dx is the same kernel
-    run with the rotated, transposed filter; the residual's gradient is dy."""
+    """y = conv2d(x, weight, bias, stride 1, padding 1) (+ residual) with frozen weight/bias, as `plan` says; dx is the same
+    kernel run with the rotated, transposed filter; the residual's gradient is dy."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual=None, stats=None):
-        x = _dev(x, "x")
+    def forward(ctx, x, weight, bias, residual, stats, plan):
         ctx.weight = weight
-        if residual is not None:
-            residual = _dev(residual, "residual")
-        return _conv3x3_run(x, weight, False, bias, residual, weight.shape[0], stats=stats)
+        return _conv3x3_run("conv3x3", _dev(x, "x"), weight, bias, _dev(residual, "residual") if residual is not None else None, plan, stats)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1347,45 +1396,34 @@ class Conv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             w = ctx.weight
             co, ci = w.shape[:2]
-            if conv3x3_wanted(dy.shape, (ci, co, 3, 3)):
-                dx = _conv3x3_run(_dev(dy, "dy"), w, True, None, None, ci)
+            plan = conv3x3_plan(dy.shape, (ci, co, 3, 3), backward=True)
+            if plan.route != "lib":
+                dx = _conv3x3_run("conv3x3 backward", _dev(dy, "dy"), w, None, None, plan)
             else:       # too few tiles for these kernels: library backward-data
                 routes.note("conv3x3.bwd_data", "lib")
                 dx = torch.nn.grad.conv2d_input((dy.shape[0], ci, dy.shape[2], dy.shape[3]), w, dy, padding=1)
-        return dx, None, None, (dy if ctx.needs_input_grad[3] else None), None
+        return dx, None, None, (dy if ctx.needs_input_grad[3] else None), None, None
 
 
 def conv3x3(x, weight, bias=None, residual=None):
-    if not conv3x3_supported(x.shape, weight.shape):
+    plan = conv3x3_plan(x.shape, weight.shape, forced=True)
+    if plan.route == "lib":
         raise ValueError(f"conv3x3: unsupported shape x {tuple(x.shape)} w {tuple(weight.shape)}")
     if weight.requires_grad or (bias is not None and bias.requires_grad):
         raise ValueError("conv3x3: the Winograd kernels serve FROZEN weights only (no weight/bias gradient)")
-    return Conv3x3Fn.apply(x, weight, bias, residual)
-
-
-GN_ONEPASS = True        # False (tests): producers leave block statistics behind even where the norm would not want them
-
-
-def _stats_useful(cout: int, h: int, w: int, groups: int = 32, rows: int = 1) -> bool:
-    """Block statistics in a convolution's epilogue only pay where the GroupNorm that follows does not hold its rows in
-    registers anyway (the one-pass form computes exact statistics from the row it has loaded; the library says which)."""
-    return not (GN_ONEPASS and cout % groups == 0 and N.lib().skp_group_norm_onepass_ok(int(rows), int(cout), int(groups), int(h * w)))
+    return Conv3x3Fn.apply(x, weight, bias, residual, None, plan)
 
 
 def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
     """The frozen blocks' 3x3 convolution (+ bias + residual): Winograd kernel where it is wanted, library
     convolution (and the fused bias+residual pass) otherwise."""
     frozen = not (weight.requires_grad or (bias is not None and bias.requires_grad))     # the kernels give no dW / db
-    if frozen and x.is_cuda and x.dtype == torch.float32 and conv3x3_wanted(x.shape, weight.shape):
-        nblk = conv3x3_stats_blocks(x.shape, weight.shape) if (want_stats and _stats_useful(weight.shape[0], x.shape[2], x.shape[3])) else 0
-        if nblk:
-            stats = torch.empty(x.shape[0], weight.shape[0], nblk, 2, device=x.device, dtype=torch.float32)
-            y = Conv3x3Fn.apply(x, weight, bias, residual, stats)
-            y._skp_blocks = (stats, nblk, 256)           # consumed by group_norm_silu (same tensor object only)
-            return y
-        return Conv3x3Fn.apply(x, weight, bias, residual)
-    if (frozen and residual is None and x.is_cuda and x.dtype == torch.float32 and CONV3X3_MODE != "lib"
-            and weight.shape[1] <= 4 and x.shape[3] % 2 == 0):
+    own = frozen and x.is_cuda and x.dtype == torch.float32
+    plan = conv3x3_plan(x.shape, weight.shape, want_stats=want_stats) if own else None
+    if own and plan.route != "lib":
+        stats = torch.empty(x.shape[0], weight.shape[0], plan.nblk, 2, device=x.device, dtype=torch.float32) if plan.nblk else None
+        return _leave_blocks(Conv3x3Fn.apply(x, weight, bias, residual, stats, plan), stats, plan.nblk, plan.pixels)
+    if own and residual is None and CONV3X3_MODE != "lib" and weight.shape[1] <= 4 and x.shape[3] % 2 == 0:
         if not (torch.is_grad_enabled() and x.requires_grad):
             return conv3x3_small(x, weight, bias, want_stats=want_stats)   # conv_in layers: output-bandwidth bound, own VALU kernel
         if conv_in_grad_ok(x, weight):           # the latent takes a gradient (keypoint guidance): its adjoint is a small-output conv
@@ -1404,60 +1442,45 @@ def conv3x3_auto(x, weight, bias=None, residual=None, want_stats=False):
 def conv3x3_gn_fold_ok(x, norm: torch.nn.GroupNorm, weight, *others) -> bool:
     """`others`: every further tensor the folded call will read (offset, bias, residual).  The folded kernel is forward
     only: with autograd on, ANY operand that requires a gradient (input, norm affine, weight, offset, bias, residual) sends
-    the block down the differentiable route."""
-    if not (x.is_cuda and x.dtype == torch.float32):
+    the block down the differentiable route.  The shape verdict is that of the plan `conv3x3_gn_silu` will execute."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or weight.requires_grad:
         return False
     if torch.is_grad_enabled() and any(t_ is not None and t_.requires_grad
                                        for t_ in (x, weight, norm.weight, norm.bias, *others)):
         return False
-    if weight.requires_grad or not conv3x3_f4_ok(x.shape, weight.shape) or not group_norm_supported(x, norm.num_groups):
-        return False
-    B, ci, H, W = x.shape
-    co = int(weight.shape[0])
-    rows = min(B, _rows_per_launch(ci, co, H, W))                        # the launch shape the batch chunks will have
-    return bool(N.lib().skp_conv3x3_f4_gn_ok(rows, ci, co, H, W)) and (B % rows == 0 or bool(
-        N.lib().skp_conv3x3_f4_gn_ok(B % rows, ci, co, H, W)))
+    return conv3x3_plan(x.shape, weight.shape, gn_fold=norm.num_groups).fold
 
 
-@torch.no_grad()
-def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, residual=None, want_stats=False):
-    """conv3x3(silu(GroupNorm(x + off))) (+ bias) (+ residual) with the normalisation applied in the convolution's patch load
-    (csrc/skp_conv_wino4.hip, GNF kernels).  Statistics come from x's producer when it left block sums behind."""
-    x = _dev(x, "x")
+def _gn_fold_coef(x, norm: torch.nn.GroupNorm, off):
+    """-> [B,C,2], the per-(row, channel) scale and shift of GroupNorm(x + off) that the folded convolution applies in its patch
+    load.  Statistics come from x's producer when it left block sums behind."""
     B, C, H, W = x.shape
-    G, cout = norm.num_groups, int(weight.shape[0])
+    G = norm.num_groups
     off_c = _dev(off.reshape(B, C), "off") if off is not None else None
-    bias = _dev(bias, "bias") if bias is not None else None
-    residual = _dev(residual, "residual") if residual is not None else None
-    if residual is not None and tuple(residual.shape) != (B, cout, H, W):
-        raise RuntimeError("conv3x3_gn_silu: residual must have the output's shape")
     mean = torch.empty(B, G, device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
     coef = torch.empty(B, C, 2, device=x.device, dtype=torch.float32)
     blocks = _blocks(x)
     routes.note("group_norm", "gn_fold")
-    routes.note("conv3x3", "wino4_c128")             # (the only form skp_conv3x3_f4_gn_ok admits)
     routes.note("group_norm.stats", "producer_blocks" if blocks is not None else "own_pass")
-    if blocks is not None:
-        bs, nblk, pix = blocks
-        _launch("skp_group_norm_coef_f32", None, off_c, norm.weight, norm.bias, mean, rstd, coef, bs, nblk, pix, None, B, C, G,
-                H * W, float(norm.eps))
-    else:
-        ws = _gn_scratch(B, G, x.device)
-        _launch("skp_group_norm_coef_f32", x, off_c, norm.weight, norm.bias, mean, rstd, coef, None, 0, 0, ws, B, C, G, H * W,
-                float(norm.eps))
-    U = _filters(weight, "f4")
-    y = torch.empty(B, cout, H, W, device=x.device, dtype=torch.float32)
-    nblk = conv3x3_stats_blocks(x.shape, weight.shape) if (want_stats and _stats_useful(cout, H, W)) else 0
-    stats = torch.empty(B, cout, nblk, 2, device=x.device, dtype=torch.float32) if nblk else None
-    chunk = _rows_per_launch(C, cout, H, W)
-    for b0 in range(0, B, chunk):
-        b1 = min(B, b0 + chunk)
-        _launch("skp_conv3x3_f4_gn_f32", x[b0:b1], U, bias, residual[b0:b1] if residual is not None else None, y[b0:b1],
-                stats[b0:b1] if stats is not None else None, coef[b0:b1], b1 - b0, C, cout, H, W)
-    if stats is not None:
-        y._skp_blocks = (stats, nblk, 256)
-    return y
+    own = blocks is None                             # the kernel reads x and a scratch buffer, or the producer's blocks
+    bs, nblk, pix = (None, 0, 0) if own else blocks
+    _launch("skp_group_norm_coef_f32", x if own else None, off_c, norm.weight, norm.bias, mean, rstd, coef, bs, nblk, pix,
+            _gn_scratch(B, G, x.device) if own else None, B, C, G, H * W, float(norm.eps))
+    return coef
+
+
+@torch.no_grad()
+def conv3x3_gn_silu(x, norm: torch.nn.GroupNorm, weight, off=None, bias=None, residual=None, want_stats=False):
+    """conv3x3(silu(GroupNorm(x + off))) (+ bias) (+ residual) with the normalisation applied in the convolution's patch load
+    (csrc/skp_conv_wino4.hip, GNF kernels): the plan's folded form, on the executor of every stride-1 route."""
+    x = _dev(x, "x")
+    bias = _dev(bias, "bias") if bias is not None else None
+    residual = _dev(residual, "residual") if residual is not None else None
+    plan = conv3x3_plan(x.shape, weight.shape, want_stats=want_stats, gn_fold=norm.num_groups)
+    stats = torch.empty(x.shape[0], weight.shape[0], plan.nblk, 2, device=x.device, dtype=torch.float32) if plan.nblk else None
+    y = _conv3x3_run("conv3x3_gn_silu", x, weight, bias, residual, plan, stats, fold=(norm, off))
+    return _leave_blocks(y, stats, plan.nblk, plan.pixels)
 
 
 def conv3x3_small(x, weight, bias=None, want_stats=False):
@@ -1473,8 +1496,7 @@ def conv3x3_small(x, weight, bias=None, want_stats=False):
     if nblk:
         stats = torch.empty(B, w.shape[0], nblk, 2, device=x.device, dtype=torch.float32)
         _launch("skp_conv3x3_small_stats_f32", x, w, bb, y, stats, B, ci, w.shape[0], H, W)
-        y._skp_blocks = (stats, nblk, 512)
-        return y
+        return _leave_blocks(y, stats, nblk, 512)
     _launch("skp_conv3x3_small_f32", x, w, bb, y, B, ci, w.shape[0], H, W)
     return y
 
@@ -1903,13 +1925,14 @@ class ConvS2Fn(torch.autograd.Function):
         w = ctx.weight
         b, c, h, wd = ctx.xshape
         co = w.shape[0]
-        if h % 2 == 0 and wd % 2 == 0 and conv3x3_wanted((b, co, h, wd), (c, co, 3, 3)):
+        plan = conv3x3_plan((b, co, h, wd), (c, co, 3, 3), backward=True) if (h % 2 == 0 and wd % 2 == 0) else None
+        if plan is not None and plan.route != "lib":
             dy = _dev(dy, "dy")
             routes.note("conv3x3_s2.bwd_data", "zero_stuffed")
             up = torch.zeros(b, co, h, wd, device=dy.device, dtype=torch.float32)
             o = 0 if ctx.pad == 1 else 1
             up[:, :, o::2, o::2] = dy
-            return _conv3x3_run(up, w, True, None, None, c), None, None, None
+            return _conv3x3_run("conv3x3_s2 backward", up, w, None, None, plan), None, None, None
         routes.note("conv3x3_s2.bwd_data", "lib")
         if ctx.pad == 1:
             return torch.nn.grad.conv2d_input(ctx.xshape, w, dy.contiguous(), stride=2, padding=1), None, None, None
@@ -1930,30 +1953,28 @@ def conv3x3_s2(x, weight, bias=None, pad: int = 0, want_stats: bool = False):
 def _conv3x3_s2_raw(x, weight, bias, pad, want_stats):
     x = _dev(x.detach(), "x")
     B, ci, H, W = x.shape
-    co = weight.shape[0]
-    y = torch.empty(B, co, H // 2, W // 2, device=x.device, dtype=torch.float32)
-    if N.lib().skp_conv3x3_s2w_ok(B, ci, co, H, W, int(pad)):       # polyphase Winograd F(4x4,2x2) where it was measured faster
-        routes.note("conv3x3_s2", "s2_wino")
-        U = _filters(weight, "s2w")
-        nblk = (H // 8) * (W // 8) // 16
-        if want_stats and nblk * 16 == (H // 8) * (W // 8):
-            stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
-            _launch("skp_conv3x3_s2w_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))
-            y._skp_blocks = (stats, nblk, 256)
-            return y
-        _launch("skp_conv3x3_s2w_f32", x, U, bias, y, B, ci, co, H, W, int(pad))
-        return y
-    routes.note("conv3x3_s2", "s2_direct")
-    U = _filters(weight, "s2")
-    if want_stats:
-        nblk = (H // 16) * (W // 32)
-        stats = torch.empty(B, co, nblk, 2, device=x.device, dtype=torch.float32)
-        _launch("skp_conv3x3_s2_stats_f32", x, U, bias, y, stats, B, ci, co, H, W, int(pad))
-        y._skp_blocks = (stats, nblk, 128)
-        return y
-    ws = _workspace("skp_conv3x3_s2_workspace", B, ci, co, H, W, device=x.device)    # small grid: K split over the input channels
-    _launch("skp_conv3x3_s2_ws_f32", x, U, bias, y, ws, B, ci, co, H, W, int(pad))
-    return y
+    dims = (B, ci, int(weight.shape[0]), H, W, int(pad))
+    # decided here, once: the kernel family (polyphase Winograd F(4x4,2x2) where it was measured faster, else the direct kernel),
+    # its ledger name and filter form, the statistics blocks per image (16 whole 4x4-output tiles / one 8 x 16 output tile each)
+    # and the pixels per block
+    if N.lib().skp_conv3x3_s2w_ok(*dims):
+        tiles = (H // 8) * (W // 8)
+        route, form, pixels, nblk = "s2_wino", "s2w", 256, (tiles // 16 if want_stats and tiles % 16 == 0 else 0)
+        entry = "skp_conv3x3_s2w_stats_f32" if nblk else "skp_conv3x3_s2w_f32"
+    else:
+        route, form, pixels, nblk = "s2_direct", "s2", 128, ((H // 16) * (W // 32) if want_stats else 0)
+        entry = "skp_conv3x3_s2_stats_f32" if nblk else "skp_conv3x3_s2_ws_f32"
+    routes.note("conv3x3_s2", route)
+    U = _filters(weight, form)
+    y = torch.empty(B, dims[2], H // 2, W // 2, device=x.device, dtype=torch.float32)
+    if nblk:
+        extra = (torch.empty(B, dims[2], nblk, 2, device=x.device, dtype=torch.float32),)
+    elif form == "s2":                                   # small grid: K split over the input channels
+        extra = (_workspace("skp_conv3x3_s2_workspace", *dims[:5], device=x.device),)
+    else:
+        extra = ()
+    _launch(entry, x, U, bias, y, *extra, *dims)
+    return _leave_blocks(y, extra[0] if nblk else None, nblk, pixels)
 
 
 class GEGLUFn(torch.autograd.Function):

@@ -36,7 +36,7 @@ _BLOCK = {"fused": "hip", "eager": "eager"}
 
 # site -> route -> kind
 ROUTES: Dict[str, Dict[str, str]] = {
-    # 3x3 / stride 1 / pad 1 convolutions of the frozen blocks (ops._conv3x3_run, ops.conv3x3_auto, ops.conv3x3_gn_silu)
+    # 3x3 / stride 1 / pad 1 convolutions of the frozen blocks (named by ops.conv3x3_plan, noted by ops._conv3x3_run / conv3x3_auto)
     "conv3x3": dict(_WINO),
     # their input gradient (ops.Conv3x3Fn.backward); the zero-stuffed stride-2 gradient runs on the same kernels and counts here too
     "conv3x3.bwd_data": dict(_WINO),

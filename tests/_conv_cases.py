@@ -570,3 +570,46 @@ def assert_plan(ops, v, ncu=256):
     for key, want in v["reach"].items():
         assert facts[key] == want, f"{v['name']}: {key} is {facts[key]}, listed as {want}"
     return facts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the decision table of ops.conv3x3_plan (test_conv_plan_host.py; the answers recorded at the commit before the plan existed are
+# tests/golden/conv_plan_table.json, one row per entry of PLAN_GRID, in this order; profiles/conv_plan.md holds the recorder)
+# ---------------------------------------------------------------------------------------------------------------------
+PLAN_SHAPES = [                                           # (B, Cin, Cout, H, W), why it is in the grid
+    ((1, 32, 32, 4, 4), "too few tiles for either Winograd form"),
+    ((2, 32, 32, 8, 8), "8 F(4x4) tiles, 32 F(2x2) tiles: under both tile rules, the own-kernels override alone takes it"),
+    ((2, 32, 32, 16, 16), "exactly 32 F(4x4) tiles with (H//4)*(W//4) % 32 != 0: F(4x4), 64-channel form, no statistics"),
+    ((2, 32, 128, 32, 32), "the smallest shape the folded kernel serves, statistics served"),
+    ((8, 320, 320, 66, 64), "H % 4 != 0: F(2x2)"),
+    ((1, 64, 96, 7, 5), "odd sides"),
+    ((1, 1280, 1280, 8, 8), "raw-filter routing, 4 tiles"),
+    ((2, 1280, 1280, 8, 8), "raw-filter routing, 8 tiles"),
+    ((3, 16, 80, 12, 12), "channel counts that are multiples of 16 but not of 32: unsupported"),
+    ((8, 4, 320, 64, 64), "a conv_in"),
+    ((8, 128, 128, 1024, 1024), "3 rows per launch: the batch in chunks of 3, 3 and a tail of 2"),
+    ((1, 128, 128, 2048, 2048), "exactly 2^31 bytes per image: refused"),
+]
+PLAN_COLUMNS = ("supported", "wanted", "f4", "f4r", "form", "kernel_route", "rows", "nblk", "fold_shape", "gn_full", "gn_tail")
+
+
+def _plan_grid():
+    import itertools
+    grid = [dict(shape=s, mode=m, own=own, onepass=one, backward=bwd, want_stats=st, raw_tiles=raw, rows_cap=None, wino_split=0)
+            for (s, _), m, own, one, bwd, st, raw in itertools.product(
+                PLAN_SHAPES, ("f4", "f2", "lib"), (False, True), (True, False), (False, True), (False, True), (0, 64))]
+    # `_rows_per_launch` patched to a constant (what test_batch_chunking_without_2gib does): chunks without 2 GiB tensors, and a
+    # full chunk whose form differs from the whole batch's (64 tiles per image: wino4_c64 per chunk, wino4_c128 for both rows),
+    # a tail the folded kernel serves (5 rows by 2) and one it does not (3 rows by 2 at 64 tiles per image: the tail is wino4_c64).
+    # No statistics rows here: the parent's statistics gate restated the 2 GiB rule and did not see the patch.
+    grid += [dict(shape=s, mode="f4", own=False, onepass=True, backward=bwd, want_stats=False, raw_tiles=0, rows_cap=cap, wino_split=0)
+             for s, cap in (((2, 32, 128, 32, 32), 1), ((5, 32, 128, 48, 48), 2), ((4, 32, 128, 48, 48), 2), ((3, 32, 128, 32, 32), 2))
+             for bwd in (False, True)]
+    # the K split forced to 1 (`wino_split`), so that the raw-filter form and the statistics epilogue both serve one shape: the
+    # launch that leaves statistics stays on the transformed filter
+    grid += [dict(shape=(1, 256, 128, 32, 32), mode="f4", own=False, onepass=False, backward=False, want_stats=st, raw_tiles=64,
+                  rows_cap=None, wino_split=1) for st in (False, True)]
+    return grid
+
+
+PLAN_GRID = _plan_grid()

@@ -265,6 +265,53 @@ def test_conv_kernel_stays_inside_its_buffers(ops, ncu, tune, monkeypatch, v):
     assert arena.intact(), f"{v['name']}: a guard band was written"
 
 
+def test_every_caller_makes_one_plan_and_runs_it(ops, monkeypatch):
+    """At (2,32,128,32,32): `conv3x3_auto` with statistics, `conv3x3_auto` on an input that takes a gradient, and that call's
+    backward each make exactly ONE `conv3x3_plan`; `conv3x3_gn_fold_ok` + `conv3x3_gn_silu` note the route their plan names; and
+    every output is bit-equal to the raw launchers called with the same filter."""
+    v, vg = A.BY_NAME["f4-c128-one-group"], A.BY_NAME["gn-c128-smallest"]
+    B, ci, co, H, W = v["shape"]
+    assert vg["shape"] == v["shape"]
+    c, cg = A.case(v, "randn"), A.case(vg, "randn")
+    monkeypatch.setattr(ops, "GN_ONEPASS", False)         # the convolution keeps its block sums at this small shape
+    plans, make = [], ops.conv3x3_plan
+    monkeypatch.setattr(ops, "conv3x3_plan", lambda *a, **k: plans.append(make(*a, **k)) or plans[-1])
+    x, w, bias, res, dy = (t.cuda() for t in (c.x, c.w, c.bias, c.res, c.dy))
+    try:
+        y = ops.conv3x3_auto(x, w, bias, res, want_stats=True)
+        assert len(plans) == 1 and plans[0][1:5] == ("wino4_c128", "f4", B, 4), plans
+        stats = torch.empty(B, co, 4, 2, device="cuda")
+        assert torch.equal(y, ops._conv3x3_f4_raw(x, ops._wino4_filters(w, False), bias, co, residual=res, stats=stats))
+        assert y._skp_blocks[1:] == (4, 256) and torch.equal(y._skp_blocks[0], stats)
+        plans.clear()
+        xg = x.clone().requires_grad_(True)
+        y2 = ops.conv3x3_auto(xg, w, bias, res)
+        assert len(plans) == 1 and plans[0].site == "conv3x3" and plans[0].nblk == 0, plans
+        assert torch.equal(y2, y) and not hasattr(y2, "_skp_blocks")
+        plans.clear()
+        dx, = torch.autograd.grad(y2, xg, dy)
+        assert len(plans) == 1 and plans[0].site == "conv3x3.bwd_data" and plans[0].route == ops.routes.wino4_form(ci, B, H, W), plans
+        assert torch.equal(dx, ops._conv3x3_f4_raw(dy, ops._wino4_filters(w, True), None, ci))
+        plans.clear()
+        norm = torch.nn.GroupNorm(A.GN_GROUPS, ci, eps=A.GN_EPS).cuda().requires_grad_(False)
+        norm.weight.copy_(cg.gamma)
+        norm.bias.copy_(cg.beta)
+        xn, wn, bn = cg.x.cuda(), cg.w.cuda(), cg.bias.cuda()
+        ops.routes.reset()
+        assert ops.conv3x3_gn_fold_ok(xn, norm, wn, None, bn, None)
+        z = ops.conv3x3_gn_silu(xn, norm, wn, bias=bn)
+        assert len(plans) == 2 and plans[0] == plans[1] and plans[1].fold, plans
+        assert ops.routes.snapshot() == {("conv3x3", plans[1].route): 1, ("group_norm", "gn_fold"): 1, ("group_norm.stats", "own_pass"): 1}
+        assert torch.equal(z, run_raw(ops, vg, cg, Arena(False))["y"])
+        torch.cuda.synchronize()
+    except RuntimeError as e:
+        if "hip" in str(e).lower():
+            pytest.exit(f"one plan per call: {e}", returncode=3)
+        raise
+    A.assert_conv_close({"y": y.cpu(), "dx": dx.cpu()}, c, "planned conv3x3_auto")
+    A.assert_conv_close({"y": z.cpu()}, cg, "planned conv3x3_gn_silu")
+
+
 def test_batch_chunking_without_2gib(ops, monkeypatch):
     """The batch-chunk loops of ops._conv3x3_run and ops.conv3x3_gn_silu (taken above 2 GiB per tensor) at 5 rows in chunks of 2, 2
     and 1: bit-equal to the five one-image calls."""
