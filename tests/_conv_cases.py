@@ -2,21 +2,28 @@
 _gpu.py).
 
 The operation under test is  y = conv2d(x, w, bias, stride 1 or 2, zero padding) (+ residual)  with a 3x3 filter, and its input
-gradient for a given dy.  Everything here runs on the CPU with plain torch ops:
+gradient for a given dy; for the kernels that came with image sampling also the stride-2 convolution of the VAE as a polyphase
+Winograd F(4x4,2x2) (kind `s2w`), nearest 2x up-sampling + convolution (`up2`), the convolution to <= 4 channels with its image
+epilogue clamp(y / 2 + 0.5, 0, 1) (`out`) and `ops.ConvInFn`, whose input gradient is that kernel (`in_fn`).  Everything here runs
+on the CPU with plain torch ops:
 
     make_input(family, shape, seed, seam)                      one fp32 activation of an input family
     check_property(family, x, seam)                            the property that makes a family hard
     case(variant, family)                                      inputs + fp64 reference + fp32 reference (kept, never modified)
     plane_err(y, y64)                                          max over (b, c) of max|y - y64| / max|y64| within that plane
     assert_conv_close(got, case, what)                         err <= M[kernel family] * err_fp32ref + 1e-7 per output
+    assert_image_close(y, img, case, what)                     the image epilogue: its own y mapped, and within the derived bound
 
 The fp32 reference runs the SAME ALGORITHM as the kernel under test, in fp32 on the CPU: the Winograd kernels get an emulation
 with the transform matrices of csrc/skp_wino4_common.h (F(4x4,3x3), points 0, +-1, +-2) or of csrc/skp_conv_wino.hip
-(F(2x2,3x3)) -- filter transform, input transform, sum over channels, inverse transform -- the direct kernels get fp32
-F.conv2d.  A kernel's error is stated as a multiple of that reference's error on the same inputs.
+(F(2x2,3x3)) -- filter transform, input transform, sum over channels, inverse transform -- the polyphase F(4x4,2x2) kernel
+one with the matrices of tests/test_conv_s2w_host.py (`s2w_emulate`), the up-sampling kernel its four folded 2x2 phase
+convolutions (`up2_emulate`), the direct kernels get fp32 F.conv2d.  A kernel's error is stated as a multiple of that
+reference's error on the same inputs.
 
 The launch plans of csrc/skp_conv_wino4.hip (wino4_use_c128 / wino4_grid / wino4_plan, wino4r_grid / wino4r_plan),
-csrc/skp_conv_wino.hip (wino_plan) and csrc/skp_conv_s2.hip (s2_splits) are restated at the end, beside
+csrc/skp_conv_wino.hip (wino_plan), csrc/skp_conv_s2.hip (s2_splits), csrc/skp_conv_s2w.hip (s2w_run: `s2w_facts`),
+csrc/skp_conv_up2.hip (`up2_facts`) and csrc/skp_conv_out.hip (`out_facts`) are restated at the end, beside
 `routes.wino4_form`, which restates the first of them for the route ledger; `assert_plan` checks every variant against the
 restatement AND against the library's own host queries.
 """
@@ -35,7 +42,8 @@ MIN_PLANE = 1e-2                                        # every fp64 plane maxim
 
 # err_kernel <= M[kernel family] * err_fp32ref + ABS_SLACK: twice the largest ratio measured on the MI355X, rounded up, never above 8
 # (profiles/conv_edges.md holds the table these follow from: largest ratios 1.21, 1.81, 2.16, 1.68, 3.14, 1.18).
-M = {"f2": 3, "f4": 4, "f4r": 5, "gn": 4, "s2": 7, "small": 3}
+# s2w, up2, out: the kernels that came with image sampling, same rule (second table there: largest ratios 2.07, 3.06, 2.91).
+M = {"f2": 3, "f4": 4, "f4r": 5, "gn": 4, "s2": 7, "small": 3, "s2w": 5, "up2": 7, "out": 6}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -43,8 +51,8 @@ M = {"f2": 3, "f4": 4, "f4r": 5, "gn": 4, "s2": 7, "small": 3}
 # ---------------------------------------------------------------------------------------------------------------------
 def impulse_sites(B, H, W, seam):
     """(b, y, x) of the impulse family: four corners, four edges, both sides of a tile seam in x and in y, the last pixel of one
-    image and the first of the next, and one more in EVERY image."""
-    sy, sx = seam
+    image and the first of the next, and one more in EVERY image.  `seam` may name further sites after (sy, sx)."""
+    sy, sx, *more = seam
     sites = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1),
              (0, 0, W // 2), (0, H - 1, W // 2), (0, H // 2, 0), (0, H // 2, W - 1)]
     if sx < W:
@@ -53,6 +61,7 @@ def impulse_sites(B, H, W, seam):
         sites += [(0, sy - 1, W // 2), (0, sy, W // 2)]
     if B > 1:
         sites += [(1, 0, 0)]                            # (0, H-1, W-1) is the last pixel of image 0
+    sites += list(more)
     sites += [(b, (5 * b + 1) % H, (3 * b + 2) % W) for b in range(B)]
     return list(dict.fromkeys(sites))
 
@@ -166,6 +175,89 @@ def zero_stuffed(dy, pad, H, W):
     return up
 
 
+# F(4x4,2x2), points 0, 1, -1, 2, inf: the matrices of tests/test_conv_s2w_host.py (csrc/skp_conv_s2w.hip)
+_W42 = {"BT": [[2, -1, -2, 1, 0], [0, -2, -1, 1, 0], [0, 2, -3, 1, 0], [0, -1, 0, 1, 0], [0, 2, -1, -2, 1]],
+        "G": [[1 / 2, 0], [-1 / 2, -1 / 2], [-1 / 6, 1 / 6], [1 / 6, 1 / 3], [0, 1]],
+        "AT": [[1, 1, 1, 1, 0], [0, 1, -1, 2, 0], [0, 1, 1, 4, 0], [0, 1, -1, 8, 1]]}
+S2W_PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))            # (row phase, column phase); a phase 1 is the one-tap phase
+S2W_TAPS = ((0, 2), (1,))                                # taps of the 3-tap filter a phase sees: (w0, w2) / (w1, 0)
+
+
+def s2w_parts(x, w, dtype=torch.float32):
+    """The two operands of the polyphase F(4x4,2x2) form of conv_s2(x, w, pad 0), per pixel phase of S2W_PHASES:
+    V = B^T d B of the 5x5 phase patches [B, C, th, tw, 5, 5] in `dtype`, and U = G g G^T of the phase's 2x2 filter [K, C, 5, 5],
+    computed in fp64 and rounded once to `dtype`, as the filter kernel does."""
+    BT = torch.tensor(_W42["BT"], dtype=dtype)
+    G = torch.tensor(_W42["G"], dtype=torch.float64)
+    B, C, H, W = x.shape
+    assert H % 8 == 0 and W % 8 == 0
+    ext = F.pad(x.to(dtype), (0, 2, 0, 2))                        # the (0,1,0,1) extension, and one more the one-tap phases' last
+    Vs, Us = [], []                                               # row / column reach: it meets a zero of U only
+    for rp, cp in S2W_PHASES:
+        d = ext[:, :, rp::2, cp::2].unfold(2, 5, 4).unfold(3, 5, 4)      # [B, C, th, tw, 5, 5]
+        assert d.shape[2:4] == (H // 8, W // 8)
+        Vs.append(BT @ d @ BT.T)
+        g = torch.zeros(w.shape[0], w.shape[1], 2, 2, dtype=torch.float64)
+        for a, ra in enumerate(S2W_TAPS[rp]):
+            for b, cb in enumerate(S2W_TAPS[cp]):
+                g[:, :, a, b] = w[:, :, ra, cb].double()
+        Us.append((G @ g @ G.T).to(dtype))
+    return Vs, Us
+
+
+def s2w_products(Vs, Us):
+    """M = sum over phases and channels of U * V per transform position -> [B, K, th, tw, 5, 5]."""
+    V, U = torch.cat(Vs, dim=1), torch.cat(Us, dim=1)            # phases along the channel axis
+    B, C4, th, tw = V.shape[:4]
+    K = U.shape[0]
+    Vp = V.permute(4, 5, 0, 2, 3, 1).reshape(25, B * th * tw, C4)
+    Up = U.permute(2, 3, 1, 0).reshape(25, C4, K)
+    return torch.bmm(Vp, Up).reshape(5, 5, B, th, tw, K).permute(2, 5, 3, 4, 0, 1)
+
+
+def s2w_finish(Mm, bias=None):
+    """Y = A^T M A per tile, tiles put together, + bias."""
+    AT = torch.tensor(_W42["AT"], dtype=Mm.dtype)
+    B, K, th, tw = Mm.shape[:4]
+    y = (AT @ Mm @ AT.T).permute(0, 1, 2, 4, 3, 5).reshape(B, K, 4 * th, 4 * tw)
+    if bias is not None:
+        y = y + bias.to(Mm.dtype)[None, :, None, None]
+    return y.contiguous()
+
+
+def s2w_emulate(x, w, bias=None, dtype=torch.float32):
+    """conv_s2(x, w, bias, pad 0) as the polyphase Winograd F(4x4,2x2) of csrc/skp_conv_s2w.hip, every step but the filter
+    transform in `dtype`."""
+    return s2w_finish(s2w_products(*s2w_parts(x, w, dtype)), bias)
+
+
+def up2_ref(x, w, bias, dtype=torch.float64):
+    return F.conv2d(F.interpolate(x.to(dtype), scale_factor=2, mode="nearest"), w.to(dtype), None if bias is None else bias.to(dtype),
+                    padding=1)
+
+
+def up2_emulate(x, w, bias=None, dtype=torch.float32):
+    """conv2d(interpolate(x, 2, nearest), w, bias, padding 1) as csrc/skp_conv_up2.hip computes it: the filter folded into four
+    2x2 phase filters in fp64 (ops.up2_fold_filter) and rounded once, then four 2x2 convolutions of the zero-padded
+    low-resolution input in `dtype`, interleaved."""
+    from stablekeypoints_amd import ops
+    Fo = ops.up2_fold_filter(w.double()).to(dtype)               # [2, 2, Co, Ci, 2, 2]
+    B, C, H, W = x.shape
+    xp = F.pad(x.to(dtype), (1, 1, 1, 1))
+    y = torch.empty(B, w.shape[0], 2 * H, 2 * W, dtype=dtype)
+    for a in range(2):
+        for c in range(2):                                        # window rows i + a - 1 + dr: a + dr in padded coordinates
+            y[:, :, a::2, c::2] = F.conv2d(xp[:, :, a:a + H + 1, c:c + W + 1], Fo[a, c])
+    if bias is not None:
+        y = y + bias.to(dtype)[None, :, None, None]
+    return y
+
+
+def image_map(y):
+    """The image epilogue of csrc/skp_conv_out.hip in y's own dtype: scale, then clamp."""
+    return (y * 0.5 + 0.5).clamp(0, 1)
+
+
 def gn_silu(x, off, gamma, beta, groups, eps, dtype):
     z = x.to(dtype)
     if off is not None:
@@ -186,8 +278,7 @@ class Case:
         g = torch.Generator().manual_seed(seed)
         self.w = torch.randn(co, ci, 3, 3, generator=g) / (3 * math.sqrt(ci))
         self.bias = torch.randn(co, generator=g) if v["bias"] else None
-        s2 = kind in ("s2", "s2_fn")
-        oh, ow = (H // 2, W // 2) if s2 else (H, W)
+        oh, ow = {"s2": (H // 2, W // 2), "s2_fn": (H // 2, W // 2), "s2w": (H // 2, W // 2), "up2": (2 * H, 2 * W)}.get(kind, (H, W))
         self.res = torch.randn(B, co, oh, ow, generator=g) if v["res"] else None
         self.gamma = self.beta = self.off = None
         if kind == "gn":
@@ -198,15 +289,20 @@ class Case:
         self.dy = make_input(family, (B, co, oh, ow), seed + 2, v["seam_out"]) if v["bwd"] else None
         self.ref64, self.ref32 = self._reference(torch.float64), self._reference(torch.float32)
         self.err32 = {name: plane_err(self.ref32[name], self.ref64[name]) for name in self.ref64}
+        self.img64 = image_map(self.ref64["y"]) if kind == "out" else None      # (not an entry of ref64: a plane of it may be all 0)
 
     def _reference(self, dtype):
         v, kind = self.v, self.v["kind"]
         B, ci, co, H, W = v["shape"]
         emulate = dtype == torch.float32
-        m = {"f2": 2, "small": 0, "s2": 0, "s2_fn": 0}.get(kind, 4)
+        m = {"f2": 2, "small": 0, "s2": 0, "s2_fn": 0, "out": 0, "in_fn": 0}.get(kind, 4)
         out = {}
         if kind in ("s2", "s2_fn"):
             out["y"] = conv_s2(self.x, self.w, self.bias, v["pad"], dtype)
+        elif kind == "s2w":
+            out["y"] = s2w_emulate(self.x, self.w, self.bias) if emulate else conv_s2(self.x, self.w, self.bias, 0, dtype)
+        elif kind == "up2":
+            out["y"] = up2_emulate(self.x, self.w, self.bias) if emulate else up2_ref(self.x, self.w, self.bias)
         else:
             x = self.x if kind != "gn" else gn_silu(self.x, self.off, self.gamma, self.beta, GN_GROUPS, GN_EPS, dtype)
             if emulate and m:
@@ -214,7 +310,9 @@ class Case:
             else:
                 y = F.conv2d(x.to(dtype), self.w.to(dtype), None if self.bias is None else self.bias.to(dtype), padding=1)
                 out["y"] = y if self.res is None else y + self.res.to(dtype)
-        if v["bwd"]:
+        if kind == "in_fn":                                   # the input gradient runs on the small-output kernel: direct, like y
+            out["dx"] = F.conv2d(self.dy.to(dtype), backward_filter(self.w).to(dtype), padding=1)
+        elif v["bwd"]:
             dy = self.dy if kind != "s2_fn" else zero_stuffed(self.dy, v["pad"], H, W)      # (the stride-2 gradient runs on the F(4x4) kernels)
             wb = backward_filter(self.w)
             out["dx"] = (winograd_emulate(dy, wb, m=m or 4) if emulate else F.conv2d(dy.double(), wb.double(), padding=1))
@@ -226,8 +324,8 @@ def _case(name, family, seed):
     return Case(BY_NAME[name], family, seed)
 
 
-def case(v, family, seed=11) -> Case:
-    return _case(v["name"], family, seed)
+def case(v, family, seed=None) -> Case:
+    return _case(v["name"], family, v["seed"] if seed is None else seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -242,9 +340,10 @@ def plane_err(y, y64) -> float:
     return ((y.double() - y64).abs().flatten(2).amax(-1) / plane_maxima(y64)).max().item()
 
 
-def whole_tensor_bound_accepts(y, y64) -> bool:
-    """The bound of the earlier convolution tests: assert_close(rtol 1e-4, atol 6e-5 * max|ref|) over the whole tensor."""
-    return bool(((y.double() - y64).abs() <= 6e-5 * y64.abs().max() + 1e-4 * y64.abs()).all())
+def whole_tensor_bound_accepts(y, y64, atol=6e-5) -> bool:
+    """The bound of the earlier convolution tests: assert_close(rtol 1e-4, atol 6e-5 * max|ref|) over the whole tensor (2e-5 in
+    test_conv_s2w_gpu.py and test_generate_gpu.py)."""
+    return bool(((y.double() - y64).abs() <= atol * y64.abs().max() + 1e-4 * y64.abs()).all())
 
 
 def input_conditions(c: Case):
@@ -280,6 +379,30 @@ def assert_conv_close(got, c: Case, what="", m=None):
             bad.append(f"{name}: {'NOT FINITE, ' if not finite else ''}err {err:.3e} > {mm} x {e32:.3e} + {ABS_SLACK:.0e}")
     assert not bad, f"{what} [{c.family}, (B,Cin,Cout,H,W)={c.v['shape']}]: " + "; ".join(bad)
     return report
+
+
+def image_errors(y, img, c: Case, m=None):
+    """The image epilogue of the small-output kernel, `img` of a launch with image=True beside `y` of the same launch without:
+      * img is bit-equal to (y * 0.5 + 0.5).clamp(0, 1) computed in fp32 from the kernel's OWN y (halving is exact, so a fused
+        multiply-add and a multiply followed by an add round alike);
+      * per plane |img - img64| <= 0.5 * (m * err32 * planemax + 1e-7) + 2^-24: y is within m * err32 + 1e-7 of y64 relative to
+        the plane's maximum, the scale is 1/2, the clamp is 1-Lipschitz, and there is one rounding at magnitude <= 1.
+    -> the list of what fails."""
+    mm = m if m is not None else M[c.v["mfam"]["y"]]
+    bad = []
+    if y.dtype != torch.float32 or img.dtype != torch.float32 or not torch.equal(img, image_map(y)):
+        bad.append("img is not clamp(y / 2 + 0.5, 0, 1) of the kernel's own y")
+    bound = 0.5 * (mm * c.err32["y"] * plane_maxima(c.ref64["y"]) + ABS_SLACK) + 2.0 ** -24       # [B, C]
+    err = (img.double() - c.img64).abs().flatten(2).amax(-1)
+    print(f"conv-edge-img {c.v['name']} {c.family}: largest |img - img64| / bound {(err / bound).max().item():.3f}")
+    if not bool(torch.isfinite(img).all()) or not bool((err <= bound).all()):
+        bad.append(f"img: |img - img64| up to {(err / bound).max().item():.3g} x the bound derived from y's")
+    return bad
+
+
+def assert_image_close(y, img, c: Case, what="", m=None):
+    bad = image_errors(y, img, c, m)
+    assert not bad, f"{what} [{c.family}, (B,Cin,Cout,H,W)={c.v['shape']}]: " + "; ".join(bad)
 
 
 def block_statistics(y, pixels_y, pixels_x):
@@ -402,26 +525,70 @@ def s2_splits(B, Cin, Cout, H, W):
     return 1 if s < 2 else s
 
 
+def s2w_facts(B, Cin, Cout, H, W, ncu=256):
+    """csrc/skp_conv_s2w.hip, s2w_run, and the id order of csrc/skp_wino4_common.h (w4_work): 16 tiles of 4x4 outputs (8x8 inputs)
+    x 128 channels per unit, no K split, one workgroup per compute unit at most."""
+    tpi = (H // 8) * (W // 8)
+    tiles = B * tpi
+    ntb, ncg = _cdiv(tiles, 16), Cout // 128
+    tbx = _cdiv(ntb, 8) if ntb >= 64 else 0
+    ids = 8 * tbx * ncg if tbx else 8 * _cdiv(ncg, 8) * ntb
+    launched = min(ids, ncu & ~7) if ncu >= 8 else ids
+    images = max((min((t + 1) * 16, tiles) - 1) // tpi - (t * 16) // tpi + 1 for t in range(ntb))
+    return {"tiles": tiles, "ntb": ntb, "ncg": ncg, "tb_per_xcd": tbx, "order": "banded" if tbx else "unit", "ids": ids,
+            "launched": launched, "persistent": ids > launched, "ragged_tb": tiles % 16 != 0, "ragged_band": bool(tbx) and 8 * tbx > ntb,
+            "idle_ids": (not tbx) and 8 * _cdiv(ncg, 8) > ncg, "images_in_a_block": images, "groups": Cin // 16,
+            "stats_ok": tpi % 16 == 0}
+
+
+def s2w_wanted(B, Cin, Cout, H, W):
+    """csrc/skp_conv_s2w.hip, s2w_shape_ok: where the library takes the polyphase kernel unasked."""
+    return Cin >= 128 and _cdiv(B * (H // 8) * (W // 8), 16) * (Cout // 128) >= 256
+
+
+def up2_facts(B, Cin, Cout, H, W):
+    """csrc/skp_conv_up2.hip: one workgroup per 8 x 16 low-resolution pixels x 32 output channels, one stage per 16 input channels."""
+    ty, tx = _cdiv(H, 8), _cdiv(W, 16)
+    return {"tiles_y": ty, "tiles_x": tx, "grid": (B * ty * tx, Cout // 32), "stages": Cin // 16, "ragged_y": H % 8 != 0,
+            "ragged_x": W % 16 != 0}
+
+
+def out_facts(B, Cin, Cout, H, W):
+    """csrc/skp_conv_out.hip: one thread per pixel pair, 256 per block, grid (blocks, B), the kernel instantiated per Cout."""
+    pairs = H * (W // 2)
+    return {"blocks": _cdiv(pairs, 256), "ragged_block": pairs % 256 != 0, "Cout": Cout, "stages": Cin // 16}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the variants: (entry point, shape, tune keys, what it must reach)
 # ---------------------------------------------------------------------------------------------------------------------
 def _v(name, kind, shape, reach, tune=None, split=True, bias=True, res=False, bwd=False, routed=None, variant=0, pad=1, off=False,
-       stats=False, ws=False):
+       stats=False, ws=False, more_sites=(), seed=11):
     B, ci, co, H, W = shape
-    mf = {"f4": "f4", "f4_stats": "f4", "gn": "gn", "f4r": "f4r", "f2": "f2", "s2": "s2", "s2_fn": "s2", "small": "small"}[kind]
+    mf = {"f4": "f4", "f4_stats": "f4", "gn": "gn", "f4r": "f4r", "f2": "f2", "s2": "s2", "s2_fn": "s2", "small": "small",
+          "s2w": "s2w", "up2": "up2", "out": "out", "in_fn": "small"}[kind]
     if kind in ("s2", "s2_fn"):
         tiles, seam, seam_out = B * (H // 16) * (W // 32), (16, 32), (8, 16)
+    elif kind == "s2w":
+        tiles, seam, seam_out = B * (H // 8) * (W // 8), (8, 8), (4, 4)
+    elif kind == "up2":
+        tiles, seam, seam_out = B * _cdiv(H, 8) * _cdiv(W, 16), (8, 16), (16, 32)
+    elif kind in ("out", "in_fn"):                        # a thread's pixel pair; `more_sites`: both sides of a block seam
+        tiles, seam, seam_out = B * _cdiv(H * (W // 2), 256), (1, 2) + tuple(more_sites), (1, 2) + tuple(more_sites)
     elif kind == "f2":
         tiles, seam, seam_out = B * ((H + 1) // 2) * ((W + 1) // 2), (2, 2), (2, 2)
     else:
         tiles, seam, seam_out = B * (H // 4) * (W // 4), (4, 4), (4, 4)
     return {"name": name, "kind": kind, "shape": shape, "reach": reach, "tune": tune or {}, "split": split, "bias": bias, "res": res,
             "bwd": bwd, "routed": routed, "variant": variant, "pad": pad, "off": off, "stats": stats, "ws": ws, "seam": seam,
-            "seam_out": seam_out, "mfam": {"y": mf, "dx": "f4" if kind == "s2_fn" else mf},
+            "seam_out": seam_out, "seed": seed, "mfam": {"y": mf, "dx": {"s2_fn": "f4", "in_fn": "out"}.get(kind, mf)}, "tiles": tiles,
             "families": BIG_FAMILIES if (kind != "small" and tiles > 1000) else FAMILIES}
 
 
 C128 = ("conv3x3", "wino4_c128")
+S2W, S2W_ROUTE = {"conv_s2w": 1}, ("conv3x3_s2", "s2_wino")
+UP2, UP2_ROUTE = {"conv_up2": 1}, ("upsample_conv", "up2_poly")
+OUT_ROUTE = {("conv_out", "small_out"): 2}               # (the plain launch and the one with the image epilogue)
 VARIANTS = [
     # ---- F(4x4,3x3), transformed filter (ops._conv3x3_f4_raw); `reach` is a subset of wino4_facts at 256 CUs
     _v("f4-c64-one-block", "f4", (2, 32, 32, 8, 8), {"form": "c64", "S": 1, "ntb": 1, "ncg": 1, "ragged_tb": True}, bwd=True),
@@ -510,6 +677,45 @@ VARIANTS = [
     _v("small-3ch-128", "small", (2, 3, 128, 16, 32), {}, routed=("conv_in", "small")),
     _v("small-3ch-128-want-stats", "small", (2, 3, 128, 16, 32), {}, routed=("conv_in", "small"), stats=True),
 ]
+# `seed`: where seed 11 leaves a condition on the INPUTS unmet (test_conv_edges_host.py, before any kernel runs), the smallest seed
+# above it that meets them all: at seed 11 one output plane of the impulse family is 9.9e-3 / 8.0e-3 of the global maximum (an
+# image with a single impulse) at the two s2w shapes, and the 120 outlier outputs of out-2ch-5x6 (~ 250 x N(0,1)) all saturate.
+VARIANTS += [
+    # ---- stride 2, polyphase Winograd F(4x4,2x2), pad 0 (skp_conv3x3_s2w_f32 / _stats_f32; ops.conv3x3_s2); reach: s2w_facts at 256 CUs
+    _v("s2w-one-tile", "s2w", (1, 16, 128, 8, 8), {"tiles": 1, "ntb": 1, "ncg": 1, "groups": 1, "ragged_tb": True}, tune=S2W, pad=0,
+       routed=S2W_ROUTE),
+    _v("s2w-three-images-in-a-block", "s2w", (3, 32, 128, 8, 16), {"tiles": 6, "images_in_a_block": 3, "groups": 2}, tune=S2W, pad=0,
+       routed=S2W_ROUTE, seed=12),
+    _v("s2w-two-cg-ragged-tb", "s2w", (3, 16, 256, 24, 24), {"tiles": 27, "ntb": 2, "ragged_tb": True, "ncg": 2, "idle_ids": True},
+       tune=S2W, pad=0, bias=False, routed=S2W_ROUTE, seed=12),
+    _v("s2w-stats-one-block", "s2w", (2, 48, 128, 32, 32), {"tiles": 32, "stats_ok": True, "groups": 3}, tune=S2W, pad=0, stats=True,
+       routed=S2W_ROUTE),
+    _v("s2w-128-channels", "s2w", (1, 128, 128, 32, 32), {"groups": 8, "ntb": 1}, tune=S2W, pad=0, routed=S2W_ROUTE),
+    _v("s2w-unit-second-unit", "s2w", (2, 16, 128, 128, 160),
+       {"ntb": 40, "order": "unit", "ids": 320, "launched": 256, "persistent": True, "stats_ok": True}, tune=S2W, pad=0, stats=True,
+       routed=S2W_ROUTE),
+    _v("s2w-banded-ragged-band", "s2w", (1, 16, 128, 208, 320),
+       {"ntb": 65, "order": "banded", "tb_per_xcd": 9, "ragged_band": True, "persistent": False}, tune=S2W, pad=0, routed=S2W_ROUTE),
+    _v("s2w-banded-persistent", "s2w", (1, 16, 128, 512, 520), {"ntb": 260, "order": "banded", "ids": 264, "persistent": True},
+       tune=S2W, pad=0, routed=S2W_ROUTE),
+    # ---- nearest 2x up-sampling + 3x3 (skp_conv3x3_up2_f32; ops.conv3x3_up2); shape: the LOW-resolution input; reach: up2_facts
+    _v("up2-one-pixel", "up2", (1, 16, 32, 1, 1), {"grid": (1, 1), "ragged_y": True, "ragged_x": True}, tune=UP2, routed=UP2_ROUTE),
+    _v("up2-odd-7x5", "up2", (2, 16, 32, 7, 5), {"grid": (2, 1), "ragged_y": True, "ragged_x": True}, tune=UP2, routed=UP2_ROUTE),
+    _v("up2-seam-9x17", "up2", (1, 32, 64, 9, 17), {"tiles_y": 2, "tiles_x": 2, "stages": 2, "grid": (4, 2)}, tune=UP2, routed=UP2_ROUTE),
+    _v("up2-wide-3x200", "up2", (1, 16, 32, 3, 200), {"tiles_x": 13, "ragged_x": True}, tune=UP2, routed=UP2_ROUTE),
+    _v("up2-exact-tiles", "up2", (3, 48, 96, 16, 32), {"grid": (12, 3), "stages": 3, "ragged_y": False, "ragged_x": False}, tune=UP2,
+       bias=False, routed=UP2_ROUTE),
+    # ---- <= 4 output channels (skp_conv3x3_small_out_f32; ops.conv3x3_small_out), each with image=False AND image=True; reach: out_facts
+    _v("out-1ch-1x2", "out", (1, 16, 1, 1, 2), {"Cout": 1, "blocks": 1}, routed=OUT_ROUTE),
+    _v("out-2ch-5x6", "out", (2, 16, 2, 5, 6), {"Cout": 2, "blocks": 1}, routed=OUT_ROUTE, seed=23),
+    _v("out-3ch-image", "out", (2, 32, 3, 16, 24), {"Cout": 3, "blocks": 1, "ragged_block": True}, routed=OUT_ROUTE),
+    _v("out-4ch-48", "out", (1, 48, 4, 8, 8), {"Cout": 4, "stages": 3}, bias=False, routed=OUT_ROUTE),
+    _v("out-3ch-three-blocks", "out", (1, 16, 3, 24, 44), {"Cout": 3, "blocks": 3, "ragged_block": True}, routed=OUT_ROUTE,
+       more_sites=((0, 11, 27), (0, 11, 28))),
+    # ---- ops.ConvInFn: conv3x3_small forward, the small-output kernel on dy with the flipped, transposed filter backward
+    _v("in-fn-4ch", "in_fn", (2, 4, 32, 12, 20), {}, bwd=True,
+       routed={("conv_in", "small"): 1, ("conv_in.bwd_data", "small_out"): 1}),
+]
 BY_NAME = {v["name"]: v for v in VARIANTS}
 assert len(BY_NAME) == len(VARIANTS)
 
@@ -523,6 +729,18 @@ def expected_ledger(v):
         led[("group_norm", "gn_fold")] = 1
         led[("group_norm.stats", "own_pass")] = 1
     return led
+
+
+def _gate_at(lib, key, gate, *dims):
+    """-> the library's answer with tune key `key` at 0 (its own choice), 1 (every shape the kernel can run) and 2 (none)."""
+    now, answers = int(lib.skp_tune_get(key)), []
+    try:
+        for value in (0, 1, 2):
+            assert lib.skp_tune_set(key, value) == 0
+            answers.append(int(gate(*dims)))
+    finally:
+        lib.skp_tune_set(key, now)
+    return tuple(answers)
 
 
 def assert_plan(ops, v, ncu=256):
@@ -564,6 +782,23 @@ def assert_plan(ops, v, ncu=256):
         assert lib.skp_conv3x3_s2_workspace(B, ci, co, H, W) == (S * out_bytes // 4 if S > 1 else 0)
         assert lib.skp_conv3x3_s2w_ok(B, ci, co, H, W, v["pad"]) == 0, "this shape belongs to the polyphase kernel"
         assert (S > 1) == v["ws"]
+    elif kind == "s2w":
+        facts = s2w_facts(B, ci, co, H, W, ncu)
+        assert v["pad"] == 0 and _gate_at(lib, b"conv_s2w", lib.skp_conv3x3_s2w_ok, B, ci, co, H, W, 0) == (int(s2w_wanted(B, ci, co, H, W)), 1, 0)
+        assert lib.skp_conv3x3_s2w_ok(B, ci, co, H, W, 1) == 0, "padding 1 belongs to the direct kernel"
+        assert facts["stats_ok"] or not v["stats"], "no statistics epilogue for this shape"
+        if not facts["stats_ok"]:                          # refused before anything is launched (the addresses are never read)
+            assert lib.skp_conv3x3_s2w_stats_f32(16, 16, None, 16, 16, B, ci, co, H, W, 0, None) == -2, "SKP_E_RANGE expected"
+    elif kind == "up2":
+        facts = up2_facts(B, ci, co, H, W)
+        assert _gate_at(lib, b"conv_up2", lib.skp_conv3x3_up2_ok, B, ci, co, H, W) == (0, 1, 0)     # (no shape is wanted unasked yet)
+    elif kind in ("out", "in_fn"):
+        facts = out_facts(B, ci, co, H, W) if kind == "out" else out_facts(B, co, ci, H, W)       # (in_fn: the backward launch)
+        if kind == "out":                                  # conv3x3_small_out_ok = a CUDA fp32 input of this shape (asked on the GPU)
+            assert ops._small_out_shape_ok(B, ci, co, W, (3, 3))
+        else:                                              # (the gate reads shapes only)
+            xm, wm = torch.empty(B, ci, H, W, device="meta"), torch.empty(co, ci, 3, 3, device="meta")
+            assert ci <= 4 and W % 2 == 0 and ops.conv_in_grad_ok(xm, wm)
     else:
         assert kind == "small" and ci <= 4 and W % 2 == 0
         facts = {"stats_blocks": int(lib.skp_conv3x3_small_stats_blocks(B, ci, co, H, W))}

@@ -1,13 +1,17 @@
 """The 3x3 convolution kernels against fp64 on hard activations (tests/_conv_cases.py): Winograd F(4x4,3x3) with transformed and
-with raw filters, its statistics epilogue and its GroupNorm-folded form, Winograd F(2x2,3x3), the direct stride-2 kernel and the
-small-input kernel -- every launch plan of each, on every input family.
+with raw filters, its statistics epilogue and its GroupNorm-folded form, Winograd F(2x2,3x3), the direct stride-2 kernel, the
+small-input kernel, and the three that came with image sampling: the polyphase Winograd F(4x4,2x2) stride-2 kernel with its
+statistics epilogue (`s2w`), nearest 2x up-sampling + convolution (`up2`) and the small-output kernel with its image epilogue
+(`out`; as the input gradient of `ops.ConvInFn`: `in_fn`) -- every launch plan of each, on every input family.
 
 Per case (kernel variant x family):
   * y (and dx where the variant has a backward-data launch) within  M[kernel family] x the per-plane error of the fp32 CPU
     reference that runs the same algorithm  (+1e-7) of fp64, everything finite;
   * a second call gives the same bits; where the variant has a routed entry (ops.conv3x3, conv3x3_gn_silu, conv3x3_s2,
-    conv3x3_small) the first call goes through it, the second through the raw entry points: same bits again, and the route
-    ledger shows the expected (site, route) once;
+    conv3x3_small, conv3x3_up2, conv3x3_small_out, ConvInFn) the first call goes through it, the second through the raw entry
+    points: same bits again, and the route ledger shows the expected (site, route) once;
+  * `out`: the launch with the image epilogue gives clamp(y / 2 + 0.5, 0, 1) of the plain launch's y, bit for bit, within the
+    bound derived from y's (A.assert_image_close);
   * the launch plan the shape was chosen for is the one the library plans (its host queries) and the restated grid describes.
 Per variant, on dc: every tensor inside NaN guard bands, output and workspace pre-filled with NaN, the workspace exactly the
 queried size: same bits, finite, guards untouched.
@@ -132,11 +136,35 @@ def run_raw(ops, v, c, arena):
         else:
             ops.N.check(lib.skp_conv3x3_s2_f32(x.data_ptr(), U.data_ptr(), ops._ptr(bias), out["y"].data_ptr(), B, ci, co, H, W,
                                                v["pad"], st), "skp_conv3x3_s2_f32")
+    elif kind == "s2w":
+        U = _filter(ops, arena, w, "skp_conv3x3_s2w_filter_f32", 81, co, ci, 0)
+        out["y"] = arena.empty(B, co, H // 2, W // 2)
+        ops.N.check(lib.skp_conv3x3_s2w_f32(x.data_ptr(), U.data_ptr(), ops._ptr(bias), out["y"].data_ptr(), B, ci, co, H, W, 0, st),
+                    "skp_conv3x3_s2w_f32")
+        if v["stats"]:
+            out["stats"], out["y_stats"] = arena.empty(B, co, (H // 8) * (W // 8) // 16, 2), arena.empty(B, co, H // 2, W // 2)
+            ops.N.check(lib.skp_conv3x3_s2w_stats_f32(x.data_ptr(), U.data_ptr(), ops._ptr(bias), out["y_stats"].data_ptr(),
+                                                      out["stats"].data_ptr(), B, ci, co, H, W, 0, st), "skp_conv3x3_s2w_stats_f32")
+    elif kind == "up2":
+        U = _filter(ops, arena, w, "skp_conv3x3_up2_filter_f32", 16, co, ci)
+        out["y"] = arena.empty(B, co, 2 * H, 2 * W)
+        ops.N.check(lib.skp_conv3x3_up2_f32(x.data_ptr(), U.data_ptr(), ops._ptr(bias), out["y"].data_ptr(), B, ci, co, H, W, st),
+                    "skp_conv3x3_up2_f32")
+    elif kind == "out":
+        for name, image in (("y", 0), ("img", 1)):
+            out[name] = arena.empty(B, co, H, W)
+            ops.N.check(lib.skp_conv3x3_small_out_f32(x.data_ptr(), w.data_ptr(), ops._ptr(bias), out[name].data_ptr(), B, ci, co, H, W,
+                                                      image, st), "skp_conv3x3_small_out_f32")
     else:
         out["y"] = arena.empty(B, co, H, W)
         ops.N.check(lib.skp_conv3x3_small_f32(x.data_ptr(), w.data_ptr(), ops._ptr(bias), out["y"].data_ptr(), B, ci, co, H, W, st),
                     "skp_conv3x3_small_f32")
-    if v["bwd"]:                                          # the same kernel on dy with the rotated, transposed filter
+    if kind == "in_fn":                                   # the small-output kernel on dy with the rotated, transposed filter
+        dy, wt = arena.put(c.dy), arena.put(A.backward_filter(c.w))
+        out["dx"] = arena.empty(B, ci, H, W)
+        ops.N.check(lib.skp_conv3x3_small_out_f32(dy.data_ptr(), wt.data_ptr(), None, out["dx"].data_ptr(), B, co, ci, H, W, 0, st),
+                    "skp_conv3x3_small_out_f32")
+    elif v["bwd"]:                                        # the same kernel on dy with the rotated, transposed filter
         dy = arena.put(c.dy if kind != "s2_fn" else A.zero_stuffed(c.dy, v["pad"], H, W))
         dx = arena.empty(B, ci, H, W)
         if kind in ("f4", "s2_fn"):
@@ -174,6 +202,20 @@ def run_routed(ops, v, c):
             out["stats"] = y._skp_blocks[0]
     elif kind == "s2_fn":
         y = ops.conv3x3_s2(x, w, bias, pad=v["pad"])
+    elif kind == "s2w":
+        y = ops.conv3x3_s2(x, w, bias, pad=0, want_stats=v["stats"])
+        assert (getattr(y, "_skp_blocks", None) is not None) == v["stats"], "statistics exactly where the variant asks for them"
+        if v["stats"]:
+            out["stats"] = y._skp_blocks[0]
+    elif kind == "up2":
+        with torch.no_grad():
+            y = ops.conv3x3_up2(x, w, bias)
+    elif kind == "out":
+        assert ops.conv3x3_small_out_ok(x, w)
+        y, out["img"] = ops.conv3x3_small_out(x, w, bias), ops.conv3x3_small_out(x, w, bias, image=True)
+    elif kind == "in_fn":
+        assert ops.conv_in_grad_ok(x, w)
+        y = ops.ConvInFn.apply(x, w, bias)
     else:
         assert kind == "small"
         y = ops.conv3x3_small(x, w, bias, want_stats=v["stats"])
@@ -228,8 +270,10 @@ def test_conv_kernel_vs_fp64(ops, ncu, tune, monkeypatch, v, family):
     for name in first:
         assert torch.isfinite(second[name]).all(), name
         assert torch.equal(first[name], second[name]), f"{v['name']} {family}: {name} differs between two calls"
-    if v["kind"] == "f4_stats":
+    if "y_stats" in second:
         assert torch.equal(second["y_stats"], second["y"]), "the statistics epilogue changes y"
+    if v["kind"] == "out":
+        A.assert_image_close(first["y"].cpu(), first["img"].cpu(), c, v["name"])
     if "stats" in second:
         check_statistics(v, second)
     print(f"conv-edge-time {v['name']} {family}: {time.perf_counter() - t0:.2f} s  {facts}")
