@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: libskp_hip.so has 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKP_LIB_PATH: another BUILD of the same library (same-box A/B of two kernel versions, tools/ab_build.py); never a fallback
 LIB_PATH = os.environ.get("SKP_LIB_PATH") or os.path.join(_HERE, "csrc", "libskp_hip.so")
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
@@ -167,12 +167,19 @@ OVERLAY_SIGNATURES = {
 }
 
 
+# include/skp_locate.h, held to it the same way (tests/test_locate_host.py)
+LOCATE_SIGNATURES = {
+    "skp_locate_workspace": [_i, _i, _i],
+    "skp_locate_f32": [_pf, _i, _i, _i, _i, _f, _pf, _pi, _vp, _i64, _vp],
+}
+
+
 def signature(name):
-    """argtypes of an entry of any of the three headers."""
-    for table in (SIGNATURES, KEYPOINT_SIGNATURES):
+    """argtypes of an entry of any of the four headers."""
+    for table in (SIGNATURES, KEYPOINT_SIGNATURES, OVERLAY_SIGNATURES):
         if name in table:
             return table[name]
-    return OVERLAY_SIGNATURES[name]
+    return LOCATE_SIGNATURES[name]
 
 
 _ERR = {-1: "SKP_E_BADARG (null pointer / non-positive size)",
@@ -196,7 +203,8 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C stablekeypoints_amd/csrc`). There is no CPU/eager fallback for the hot path.")
     l = C.CDLL(LIB_PATH)
-    for name, argtypes in (*SIGNATURES.items(), *KEYPOINT_SIGNATURES.items(), *OVERLAY_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *KEYPOINT_SIGNATURES.items(), *OVERLAY_SIGNATURES.items(),
+                           *LOCATE_SIGNATURES.items()):
         if not hasattr(l, name):
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(l, name)

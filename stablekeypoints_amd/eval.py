@@ -1,6 +1,9 @@
-"""Arg-max helpers with the reference's names/semantics (eval.py:39-111), running on the HIP
-token-statistics kernel (csrc/skp_select_loss.hip).  The rest of the reference's eval.py (dataset
-metrics, plotting) is out of scope."""
+"""The reference's eval.py: arg-max helpers with its names / semantics (eval.py:39-111) on the HIP token-statistics kernel
+(csrc/skp_select_loss.hip), the augmented inference (:197-355), and the evaluation stage -- `locate_keypoints` (one fused pass from a
+whole group's maps to locations, csrc/skp_locate.hip), `find_corresponding_points` (:159-195), `swap_points` (:360-371),
+`keypoint_errors` (the five dataset metrics of :452-494) and `evaluate` (:374-523).  NOT built: the reference's dataset classes
+(`evaluate` takes any `{"img", "kpts"[, "visibility"]}` dataset, e.g. `custom_images.AnnotatedImages`), wandb logging, and the debug
+figure of `visualize=True`."""
 from __future__ import annotations
 
 import torch
@@ -188,3 +191,147 @@ def finish_augmented(tot, num, reduce=True):
     out = tot / num
     out[out != out] = 0
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation stage: maps -> locations -> regressed keypoints -> dataset error       eval.py:113-195, 360-523
+# ---------------------------------------------------------------------------------------------
+STRATEGIES = ("argmax", "weighted_avg")
+METHODS = ("inter_eye_distance", "visible", "mean_average_error", "pck", "orientation_invariant")
+
+
+def locate_formula(maps, strategy="argmax", distance=5):
+    """The definition of include/skp_locate.h in torch ops, in the dtype of `maps` and without writing into it: [N,h,w] ->
+    (loc [N,2] = (row, col) in pixels, flat int64 [N]).  The op order is the reference's (eval.py:113-155: normalise by the
+    window's sum + 1e-6, then the weighted sums); the window test is the reference's expression in fp32, whatever the dtype of the
+    maps.  In fp64 this is the definition."""
+    n, h, w = maps.shape
+    flat = torch.argmax(maps.reshape(n, -1), dim=-1)
+    rs, cs = flat // w, flat % w
+    if strategy == "argmax":
+        return torch.stack([rs, cs], dim=-1).to(maps.dtype) + 0.5, flat
+    r = torch.arange(h, device=maps.device).view(1, h, 1)
+    c = torch.arange(w, device=maps.device).view(1, 1, w)
+    m = maps
+    if distance != -1:
+        d2 = (r - rs.view(n, 1, 1)) ** 2 + (c - cs.view(n, 1, 1)) ** 2
+        inside = torch.sqrt(d2.to(torch.float32)) <= torch.tensor(float(distance), dtype=torch.float32, device=maps.device)
+        m = torch.where(inside, maps, torch.zeros((), dtype=maps.dtype, device=maps.device))
+    norm = m / (torch.sum(m, dim=[1, 2], keepdim=True) + 1e-6)
+    r, c = r.to(maps.dtype), c.to(maps.dtype)
+    return torch.stack([torch.sum(r * norm, dim=[1, 2]), torch.sum(c * norm, dim=[1, 2])], dim=-1) + 0.5, flat
+
+
+def locate_keypoints(maps, strategy="argmax", distance=5):
+    """[..., h, w] -> [..., 2]: per map (row + 0.5, col + 0.5) of the first maximal element (`argmax`: eval.py:39-60), or the
+    intensity-weighted mean location over the pixels within `distance` of it, -1 for the whole map (`weighted_avg`:
+    eval.py:113-155), in pixels.  One launch for all the maps (ops.locate, include/skp_locate.h); `maps` is not modified, unlike
+    `pixel_from_weighted_avg`'s argument.  Host tensors and other dtypes evaluate `locate_formula`."""
+    if strategy not in STRATEGIES:
+        raise ValueError(f"strategy must be one of {STRATEGIES}, got {strategy!r}")
+    if maps.dim() < 2 or maps.numel() == 0:
+        raise ValueError(f"locate_keypoints: expected [..., h, w] with elements, got {tuple(maps.shape)}")
+    if strategy == "weighted_avg" and not (distance >= 0 or distance == -1):
+        raise ValueError(f"distance must be >= 0, or -1 for the whole map, got {distance!r}")
+    lead, (h, w) = maps.shape[:-2], maps.shape[-2:]
+    if maps.is_cuda and maps.dtype == torch.float32:
+        _routes.note("eval.locate", "locate")
+        loc, _ = ops.locate(maps, STRATEGIES.index(strategy), distance)
+    else:
+        _routes.note("eval.locate", "host")
+        loc, _ = locate_formula(maps.detach().reshape(-1, h, w), strategy, distance)
+    return loc.reshape(*lead, 2)
+
+
+def find_corresponding_points(maps, num_points=10):
+    """eval.py:159-195: maps [n,T,h,w] -> (points [n,num_points,2] = (row, col) in [0, 1], the `num_points` tokens of lowest entropy).
+    The entropy is that of torch.distributions.Categorical(probs = softmax over the pixels) per map (probabilities renormalised,
+    their logarithm clamped at the dtype's eps), summed over the images; the points are the arg-max locations of the chosen
+    tokens' maps, one locator launch, divided by (h, w): what `visualize.plot_point_correspondences` takes (the reference returns
+    them in pixels)."""
+    n, T, h, w = maps.shape
+    sm = torch.softmax(maps.reshape(n * T, h * w), dim=-1)
+    probs = sm / sm.sum(dim=-1, keepdim=True)
+    eps = torch.finfo(probs.dtype).eps
+    entropy = -(torch.log(probs.clamp(min=eps, max=1 - eps)) * probs).sum(dim=-1).reshape(n, T).sum(dim=0)
+    chosen = torch.argsort(entropy)[:num_points]
+    pts = locate_keypoints(maps[:, chosen].contiguous(), "argmax")
+    return pts / torch.tensor([float(h), float(w)], dtype=pts.dtype, device=pts.device), chosen
+
+
+SWAP_PAIRS = [(1, 6), (2, 7), (3, 8), (4, 9), (5, 10), (17, 25), (18, 26), (19, 27), (20, 28), (21, 28), (22, 30), (23, 31)]
+
+
+def swap_points(points):
+    """eval.py:360-371: the left / right swap of the 32 Human3.6M joints, points [B,N,D].  The pairs are the reference's as
+    written, (21, 28) after (20, 28) included: joint 28 ends up taking 21, 20 takes 28 and 21 takes 28."""
+    permutation = list(range(points.shape[1]))
+    for a, b in SWAP_PAIRS:
+        permutation[a] = b
+        permutation[b] = a
+    return points[:, permutation, :]
+
+
+def keypoint_errors(locations, regressor, gt, visibility=None, method="inter_eye_distance"):
+    """eval.py:452-494 for all images at once: locations [N,K,2] in [0, 1], regressor [2K,2G], gt [N,G,2] in [0, 1], visibility
+    [N,G] or None (ones) -> the error of every image [N], in torch on the device and in the dtype of `locations`.
+        est = ((locations.view(N, -1) - 0.5) @ regressor + 0.5).view(N, G, 2);  l2 = |est - gt| per keypoint
+        inter_eye_distance      mean of l2 / |gt[0] - gt[1]|
+        visible                 sum(l2 vis) / sum(vis)                (an image without a visible keypoint: NaN, as the reference)
+        mean_average_error      sum(l2 vis), est and gt times 256
+        pck                     mean of (l2 < 6), est and gt times 256
+        orientation_invariant   128 min(mean l2, mean l2 of `swap_points(est)`)
+    Another method raises ValueError (the reference dies with a NameError after its first image)."""
+    if method not in METHODS:
+        raise ValueError(f"evaluation method must be one of {METHODS}, got {method!r}")
+    N = locations.shape[0]
+    regressor, gt = regressor.to(locations), gt.to(locations)
+    est = ((locations.reshape(N, -1) - 0.5) @ regressor + 0.5).reshape(N, -1, 2)
+    if est.shape != gt.shape:
+        raise ValueError(f"the regressor gives {tuple(est.shape)} keypoints, the annotations are {tuple(gt.shape)}")
+    if method in ("mean_average_error", "pck"):
+        est, gt = est * 256, gt * 256
+    l2 = (est - gt).norm(dim=-1)
+    if method == "inter_eye_distance":
+        return (l2 / torch.sqrt(torch.sum((gt[:, 0] - gt[:, 1]) ** 2, dim=-1, keepdim=True))).mean(dim=1)
+    if method in ("visible", "mean_average_error"):
+        vis = torch.ones_like(l2) if visibility is None else visibility.to(l2)
+        total = (l2 * vis).sum(dim=1)
+        return total / vis.sum(dim=1) if method == "visible" else total
+    if method == "pck":
+        return (l2 < 6).to(l2.dtype).mean(dim=1)
+    mean, swapped = l2.mean(dim=1), (swap_points(est) - gt).norm(dim=-1).mean(dim=1)
+    return torch.where(swapped < mean, swapped, mean) * 128
+
+
+@torch.no_grad()
+def evaluate(ldm, context, indices, regressor, args, controllers, num_gpus, from_where=["down_cross", "mid_cross", "up_cross"],
+             dataset=None, routes="off", draws=None):
+    """eval.py:374-523 -> (mean error, all_errors [N] on the host).  Per image of the test set: the augmented maps of the voted
+    tokens, their locations (`args.max_loc_strategy`), the regressed keypoints, the error under `args.evaluation_method`
+    (`keypoint_errors`).  The dataset loop is `precompute_all_keypoints`'s with `batched_locator=True`: groups of
+    `args.images_per_forward` images in one network batch and one locator launch, the images sharded over the ranks, one gather;
+    every image of the dataset is taken (`args.max_num_points` bounds the regressor's training set, not this).
+    `all_errors.pt` goes to `args.save_folder` when that is set (rank 0 writes).
+    ORDER: the errors come out in DATASET order (all_errors[i] belongs to dataset[i]); the reference's come out in the order of its
+    shuffled loader, which it does not record.  The mean is the same.
+    `dataset`: any `{"img", "kpts"[, "visibility"]}` dataset (default: `build_dataset(args)`; one without "kpts" raises).
+    `draws = (order, noise, thetas)`: as `precompute_all_keypoints` (parity tests; the errors then come out in `order`).
+    `routes`: "off" | "report" | "strict", the route ledger's rule for this call (`routes.guard`)."""
+    import os
+    from . import dist as skp_dist
+    from . import keypoint_regressor as KR
+    method = getattr(args, "evaluation_method", "inter_eye_distance")
+    if method not in METHODS:
+        raise ValueError(f"evaluation method must be one of {METHODS}, got {method!r}")
+    with _routes.guard(routes):
+        source, targets, vis = KR._precompute_all_keypoints(ldm, context, indices, args, controllers, num_gpus, from_where, dataset,
+                                                            draws, batched_locator=True, whole_dataset=True)
+        if targets is None:
+            raise ValueError("evaluate: the dataset's items carry no 'kpts'")
+        errors = keypoint_errors(source, regressor.to(source.device), targets.to(source.device), vis, method).cpu()
+    folder = getattr(args, "save_folder", None)
+    if folder and skp_dist.rank() == 0:
+        os.makedirs(folder, exist_ok=True)
+        torch.save(errors, os.path.join(folder, "all_errors.pt"))
+    return float(errors.mean()), errors

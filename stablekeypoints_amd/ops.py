@@ -1713,6 +1713,23 @@ def map_range(maps):
     return out
 
 
+def locate(maps, mode: int = 0, distance: float = 5.0):
+    """float [..., h, w] -> (loc float32 [N,2] = (row, col) in pixels, flat int32 [N]) of each of the N = prod(leading dims) maps:
+    the first maximal element, and the location `mode` makes of it -- 0: its centre; 1: the intensity-weighted mean over the
+    pixels within `distance` of it (-1: the whole map).  One pass, `maps` is only read; the same bits on every call
+    (csrc/skp_locate.hip; the definition is in include/skp_locate.h and, in torch, `eval.locate_formula`)."""
+    maps = _dev(maps.detach(), "maps")
+    if maps.dim() < 2 or maps.numel() == 0:
+        raise RuntimeError(f"locate: expected [..., h, w] with elements, got {tuple(maps.shape)}")
+    h, w = maps.shape[-2:]
+    n = maps.numel() // (h * w)
+    loc = torch.empty(n, 2, device=maps.device, dtype=torch.float32)
+    flat = torch.empty(n, device=maps.device, dtype=torch.int32)
+    ws = _workspace("skp_locate_workspace", n, h, w, device=maps.device)
+    _launch("skp_locate_f32", maps, n, h, w, int(mode), float(distance), loc, flat, ws, 0 if ws is None else 4 * ws.numel())
+    return loc, flat
+
+
 def overlay_u8(img, maps=None, rng=None, lut=None, alpha: float = 0.7, pts=None, colors=None, glyphs=None, radius: float = 9.0,
                ring: float = 1.5, labels: bool = True, out=None, origin=(0, 0), cols: int = 1, gap: int = 0):
     """Images under an optional colour-mapped heat map and numbered markers, as bytes in a canvas (csrc/skp_overlay.hip; the

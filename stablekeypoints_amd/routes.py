@@ -79,6 +79,9 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # kernels (ops.map_range, ops.overlay_u8) / visualize.range_formula, visualize.overlay_formula in torch on host tensors
     "visualize.range": {"map_range": "hip", "host": "host"},
     "visualize.overlay": {"overlay_u8": "hip", "host": "host"},
+    # eval.locate_keypoints: the maps of a whole group of images -> peak locations (arg-max or the weighted mean around it): the
+    # locator kernel (ops.locate) / eval.locate_formula in torch on host tensors and other dtypes
+    "eval.locate": {"locate": "hip", "host": "host"},
     "attn.cross": {"ca_token_split": "hip", "ca_plain": "hip", "flash": "hip", "host": "host"},
     "attn.self": {"fused_qkv": "hip", "plain": "hip", "host": "host"},
     "flash.fwd": dict(_FLASH),
