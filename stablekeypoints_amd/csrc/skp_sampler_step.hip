@@ -11,7 +11,11 @@
 // capped at 2048 workgroups with a grid-stride loop.  Every output element is computed by the lane that read its inputs, after
 // reading them, which is what makes y == x and x0_out == x0_prev legal.
 // Also here: skp_axpby_f32, the plain unguided epsilon form of the DDIM update, x_prev = c1 x + c2 eps with host-computed coefficients.
+// Device-row forms (include/skp_sampler_graph.h; the captured sampling loop): the same kernel body behind a second __global__ that
+// first reads this step's StepCoef from row *step of a table in device memory, where the by-value kernel receives it as an
+// argument.  `step_one` and the loop around it are shared, so equal floats give equal bits.  skp_step_advance moves the counter.
 #include "skp_common.h"
+#include "../../include/skp_sampler_graph.h"
 
 namespace {
 
@@ -69,9 +73,8 @@ __device__ __forceinline__ float step_one(float x, float mc, float mu, float p, 
 // Y2VEC: the second copy y + n is 16-byte aligned too (n % 4 == 0); otherwise it is written with scalar stores.
 // x / y and x0_prev / x0_out carry no __restrict__: each pair may be one buffer.
 template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL, bool KP = false>
-__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const float* x, const float* __restrict__ mc,
-                                                                        const float* __restrict__ mu, StepExtra<FULL> e, float* y,
-                                                                        long long n, int copies, StepCoef c) {
+__device__ __forceinline__ void step_body(const float* x, const float* __restrict__ mc, const float* __restrict__ mu,
+                                          const StepExtra<FULL>& e, float* y, long long n, int copies, const StepCoef& c) {
     const long long tid = (long long)blockIdx.x * SKP_EW_BLOCK + threadIdx.x;
     const long long stride = (long long)gridDim.x * SKP_EW_BLOCK;
     float* y2 = copies == 2 ? y + n : nullptr;
@@ -141,21 +144,61 @@ __global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const fl
     }
 }
 
+template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL, bool KP = false>
+__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_kernel(const float* x, const float* __restrict__ mc,
+                                                                        const float* __restrict__ mu, StepExtra<FULL> e, float* y,
+                                                                        long long n, int copies, StepCoef c) {
+    step_body<GUIDED, VEC, Y2VEC, FULL, KP>(x, mc, mu, e, y, n, copies, c);
+}
+
+// The device-row form: StepCoef from row *step of `table` ([steps, SKP_STEP_ROW]: sa sb cx c0 ce c1 cn guidance), this step's noise
+// at noise + *step * n.  A term whose coefficient is 0 loses its pointer here, before the body: the body then neither reads the
+// buffer nor sees what it holds (p / nz are 0, as for the by-value entry's null pointers).  *step and the row are the same for
+// every lane of the grid, so these branches are uniform.  A counter outside the table: nothing is read or written.
+template <bool GUIDED, bool VEC, bool Y2VEC, bool FULL, bool KP = false>
+__global__ __launch_bounds__(SKP_EW_BLOCK) void skp_sampler_step_dev_kernel(const float* x, const float* __restrict__ mc,
+                                                                            const float* __restrict__ mu, StepExtra<FULL> e, float* y,
+                                                                            long long n, int copies, const float* __restrict__ table,
+                                                                            const int* __restrict__ step, int steps, int prediction,
+                                                                            int clip) {
+    const int s = *step;
+    if (s < 0 || s >= steps) return;
+    const float* __restrict__ r = table + (long long)s * SKP_STEP_ROW;
+    StepCoef c;
+    c.g = r[7], c.sa = r[0], c.sb = r[1], c.c0 = r[3], c.ce = r[4];
+    c.cx = FULL ? r[2] : 0.f, c.c1 = FULL ? r[5] : 0.f, c.cn = FULL ? r[6] : 0.f;
+    c.kr = KP ? (float)((double)c.sb / (double)c.sa) : 0.f;
+    c.prediction = prediction, c.clip = clip;
+    if constexpr (FULL) {
+        if (c.c1 == 0.f) e.x0_prev = nullptr;
+        e.noise = (c.cn == 0.f || !e.noise) ? nullptr : e.noise + (long long)s * n;
+    }
+    step_body<GUIDED, VEC, Y2VEC, FULL, KP>(x, mc, mu, e, y, n, copies, c);
+}
+
 // The alignment decision, the grid and the launch for both entries, which have checked their arguments.  `full`: the sampler form;
 // otherwise x0_prev, noise and x0_out are null and the kernel does not take them.  `kg` (sampler form only): the guidance gradient,
 // with its `rows` scales `kgs`; null for the two entries without it.
 int step_launch(bool full, const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise, float* y,
                 float* x0_out, int64_t n, int copies, const StepCoef& c, void* stream, const float* kg = nullptr,
-                const float* kgs = nullptr, int rows = 1) {
+                const float* kgs = nullptr, int rows = 1, const float* table = nullptr, const int* step = nullptr, int steps = 0) {
+    // (device-row form: `noise` is the base of [steps, n], and its rows are 16-byte aligned with it only when n % 4 == 0)
     const bool vec = skp_aligned16(x) && skp_aligned16(m_c) && skp_aligned16(m_u) && skp_aligned16(x0_prev) && skp_aligned16(noise) &&
-                     skp_aligned16(y) && skp_aligned16(x0_out) && skp_aligned16(kg) && n >= 4;
+                     skp_aligned16(y) && skp_aligned16(x0_out) && skp_aligned16(kg) && n >= 4 &&
+                     !(table && noise && (n & 3) != 0);
     const long long per = n / rows;
     const bool y2vec = (n & 3) == 0;
     const dim3 grid(skp_capped_grid(vec ? n / 4 : n)), block(SKP_EW_BLOCK);
     hipStream_t st = (hipStream_t)stream;
 #define SKP_STEP_AS(G, V, Y2, FULL, KP, ...)                                                                                           \
-    hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2, FULL, KP>), grid, block, 0, st, x, m_c, m_u, StepExtra<FULL>{__VA_ARGS__}, y, \
-                       (long long)n, copies, c)
+    do {                                                                                                                               \
+        if (table)                                                                                                                     \
+            hipLaunchKernelGGL((skp_sampler_step_dev_kernel<G, V, Y2, FULL, KP>), grid, block, 0, st, x, m_c, m_u,                     \
+                               StepExtra<FULL>{__VA_ARGS__}, y, (long long)n, copies, table, step, steps, c.prediction, c.clip);       \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((skp_sampler_step_kernel<G, V, Y2, FULL, KP>), grid, block, 0, st, x, m_c, m_u,                         \
+                               StepExtra<FULL>{__VA_ARGS__}, y, (long long)n, copies, c);                                              \
+    } while (0)
 #define SKP_STEP(G, V, Y2)                                                                      \
     do {                                                                                        \
         if (kg) SKP_STEP_AS(G, V, Y2, true, true, x0_prev, noise, x0_out, kg, kgs, per);        \
@@ -180,6 +223,25 @@ __global__ __launch_bounds__(256) void skp_axpby_kernel(const float* __restrict_
                                                         float* __restrict__ y, long long n, float ca, float cb) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] = ca * x[i] + cb * z[i];
+}
+
+// the same expression with (ca, cb) = (cx, ce) of row *step
+__global__ __launch_bounds__(256) void skp_axpby_dev_kernel(const float* __restrict__ x, const float* __restrict__ z,
+                                                            float* __restrict__ y, long long n, const float* __restrict__ table,
+                                                            const int* __restrict__ step, int steps) {
+    const int s = *step;
+    if (s < 0 || s >= steps) return;
+    const float ca = table[(long long)s * SKP_STEP_ROW + 2], cb = table[(long long)s * SKP_STEP_ROW + 4];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = ca * x[i] + cb * z[i];
+}
+
+// one lane; the value goes through a vector register (volatile: a plain global load and store, nothing the compiler may move)
+__global__ __launch_bounds__(64) void skp_step_advance_kernel(volatile int* step) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int v = *step;
+        *step = v + 1;
+    }
 }
 
 }  // namespace
@@ -221,5 +283,52 @@ extern "C" int skp_axpby_f32(const void* x, const void* z, void* y, int64_t n, f
     if (n > (int64_t)0x7fffffff * 256) return SKP_E_RANGE;
     hipLaunchKernelGGL(skp_axpby_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        (const float*)z, (float*)y, (long long)n, a, b);
+    return skp_launch_status();
+}
+
+// ---- device-row forms (include/skp_sampler_graph.h) ----
+extern "C" int skp_axpby_dev_f32(const float* x, const float* z, float* y, int64_t n, const float* table, const int32_t* step,
+                                 int steps, void* stream) {
+    if (!x || !z || !y || n <= 0 || !table || !step || steps <= 0) return SKP_E_BADARG;
+    if (n > (int64_t)0x7fffffff * 256) return SKP_E_RANGE;
+    hipLaunchKernelGGL(skp_axpby_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, z, y,
+                       (long long)n, table, (const int*)step, steps);
+    return skp_launch_status();
+}
+
+extern "C" int skp_ddim_step_dev_f32(const float* x, const float* m_c, const float* m_u, float* y, int64_t n, int copies,
+                                     int prediction, int clip, const float* table, const int32_t* step, int steps, void* stream) {
+    if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
+    if (!table || !step || steps <= 0) return SKP_E_BADARG;
+    const StepCoef c{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, prediction, clip ? 1 : 0};      // (the kernel fills the floats)
+    return step_launch(false, x, m_c, m_u, nullptr, nullptr, y, nullptr, n, copies, c, stream, nullptr, nullptr, 1, table,
+                       (const int*)step, steps);
+}
+
+extern "C" int skp_sampler_step_dev_f32(const float* x, const float* m_c, const float* m_u, const float* x0_prev, const float* noise,
+                                        float* y, float* x0_out, int64_t n, int copies, int prediction, int clip, const float* table,
+                                        const int32_t* step, int steps, void* stream) {
+    if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
+    if (!table || !step || steps <= 0) return SKP_E_BADARG;
+    const StepCoef c{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, prediction, clip ? 1 : 0};
+    return step_launch(true, x, m_c, m_u, x0_prev, noise, y, x0_out, n, copies, c, stream, nullptr, nullptr, 1, table,
+                       (const int*)step, steps);
+}
+
+extern "C" int skp_sampler_step_kp_dev_f32(const float* x, const float* m_c, const float* m_u, const float* x0_prev,
+                                           const float* noise, float* y, float* x0_out, int64_t n, int copies, int prediction,
+                                           int clip, const float* table, const int32_t* step, int steps, const float* g,
+                                           const float* gs, int rows, void* stream) {
+    if (!x || !m_c || !y || n <= 0 || (copies != 1 && copies != 2) || prediction < 0 || prediction > 2) return SKP_E_BADARG;
+    if (!table || !step || steps <= 0) return SKP_E_BADARG;
+    if (!g || !gs || rows <= 0 || n % rows != 0) return SKP_E_BADARG;
+    const StepCoef c{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, prediction, clip ? 1 : 0};
+    return step_launch(true, x, m_c, m_u, x0_prev, noise, y, x0_out, n, copies, c, stream, g, gs, rows, table, (const int*)step,
+                       steps);
+}
+
+extern "C" int skp_step_advance(int32_t* step, void* stream) {
+    if (!step) return SKP_E_BADARG;
+    hipLaunchKernelGGL(skp_step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (volatile int*)step);
     return skp_launch_status();
 }

@@ -67,6 +67,17 @@ def step_formula(x, m_c, m_u, coef, guidance, prediction_type, clip, x0_prev=Non
     return y, x0
 
 
+STEP_ROW = 8                                 # SKP_STEP_ROW of include/skp_sampler_graph.h
+
+
+def pack_step_table(coefs, guidance: float = 1.0) -> torch.Tensor:
+    """The rows of a plan as the device-row step kernels read them (include/skp_sampler_graph.h): float32 [steps, STEP_ROW] on the
+    host, row i = (sa, sb, cx, c0, ce, c1, cn, guidance) of `coefs[i]` -- fp64 host numbers, each rounded to float32 ONCE, which is
+    what the by-value entries make of the same numbers in their argument lists.  A `cx` of None (the DDIM form) is stored as 0."""
+    rows = [[float(0.0 if v is None else v) for v in c] + [float(guidance)] for c in coefs]
+    return torch.tensor(rows, dtype=torch.float64).reshape(len(rows), STEP_ROW).to(torch.float32)
+
+
 def is_stochastic(kind: str, eta: float = 0.0) -> bool:
     return kind == "dpm++2m-sde" or (kind == "ddim" and eta > 0)
 

@@ -1687,6 +1687,86 @@ def sampler_step(x, m_c, m_u=None, *, x0_prev=None, noise=None, coef, guidance: 
     return out
 
 
+STEP_ROW = 8                   # SKP_STEP_ROW of include/skp_sampler_graph.h: sa sb cx c0 ce c1 cn guidance
+
+
+def _step_row(who, table, step, steps):
+    """The device row of the `*_dev` steps, checked on the host as far as the host can: `table` float32 [rows, STEP_ROW] and
+    contiguous, `step` ONE int32, both on the device, and at least `steps` rows -- the count of the plan the counter walks, which
+    is also what the kernel holds the counter to.  -> int(steps)."""
+    steps = int(steps)
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float32 and table.is_contiguous()
+            and table.dim() == 2 and table.shape[1] == STEP_ROW):
+        raise RuntimeError(f"{who}: `table` must be a contiguous float32 device tensor [steps, {STEP_ROW}]")
+    if not (isinstance(step, torch.Tensor) and step.is_cuda and step.dtype == torch.int32 and step.numel() == 1):
+        raise RuntimeError(f"{who}: `step` must be one int32 on the device")
+    if steps < 1 or table.shape[0] < steps:
+        raise ValueError(f"{who}: a table of {table.shape[0]} rows for a plan of {steps} steps")
+    return steps
+
+
+def step_advance(step):
+    """*step += 1 on the device (skp_step_advance): the last launch of a recorded sampling step."""
+    if not (isinstance(step, torch.Tensor) and step.is_cuda and step.dtype == torch.int32 and step.numel() == 1):
+        raise RuntimeError("step_advance: `step` must be one int32 on the device")
+    _launch("skp_step_advance", step)
+    return step
+
+
+def axpby_dev(x, z, *, table, step, steps, out=None):
+    """`axpby` with a = cx and b = ce of row *step of `table` (skp_axpby_dev_f32).  `out`: may be x or z."""
+    x, z = _dev(x, "x"), _dev(z, "z")
+    if x.shape != z.shape:
+        raise RuntimeError("axpby_dev: shapes differ")
+    steps = _step_row("axpby_dev", table, step, steps)
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.numel()):
+        raise RuntimeError("axpby_dev: `out` must be a contiguous float32 device tensor of x.numel() elements")
+    _launch("skp_axpby_dev_f32", x, z, out, x.numel(), table, step, steps)
+    return out
+
+
+def ddim_step_dev(x, m_c, m_u=None, *, table, step, steps, prediction="epsilon", clip: bool = False, copies: int = 1, out=None):
+    """`ddim_step` with (sa, sb, pa, pb, guidance) = columns (0, 1, 3, 4, 7) of row *step of `table` (skp_ddim_step_dev_f32): for
+    equal floats, the bits of `ddim_step`."""
+    x, m_c, m_u, _, pred, n, out = _step_args("ddim_step_dev", x, m_c, m_u, None, None, prediction, copies, out)
+    steps = _step_row("ddim_step_dev", table, step, steps)
+    _launch("skp_ddim_step_dev_f32", x, m_c, m_u, out, n, copies, pred, bool(clip), table, step, steps)
+    return out
+
+
+def sampler_step_dev(x, m_c, m_u=None, *, x0_prev=None, noise=None, table, step, steps, prediction="epsilon", clip: bool = False,
+                     copies: int = 1, out=None, x0_out=None, grad=None, grad_scale=None):
+    """`sampler_step` with its row (sa, sb, cx, c0, ce, c1, cn, guidance) read by the kernel from row *step of `table`
+    (skp_sampler_step_dev_f32 / skp_sampler_step_kp_dev_f32, include/skp_sampler_graph.h): for equal floats, the bits of
+    `sampler_step`.  `noise`: ALL steps' gaussians, [>= steps, *x.shape]; the kernel takes row *step.  `x0_prev` / `noise` are read
+    only on steps whose c1 / cn is not 0, whatever they hold on the others; None says that no row has a nonzero coefficient.
+    Everything else as for `sampler_step`."""
+    x, m_c, m_u, _, pred, n, out = _step_args("sampler_step_dev", x, m_c, m_u, x0_prev, None, prediction, copies, out)
+    steps = _step_row("sampler_step_dev", table, step, steps)
+    if noise is not None:
+        if not (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()):
+            raise RuntimeError("sampler_step_dev: `noise` must be a contiguous float32 device tensor")
+        if noise.dim() != x.dim() + 1 or noise.shape[1:] != x.shape or noise.shape[0] < steps:
+            raise ValueError(f"sampler_step_dev: noise {tuple(noise.shape)} is not [>= {steps}, {', '.join(map(str, x.shape))}]")
+    if x0_out is not None and not (x0_out.is_cuda and x0_out.dtype == torch.float32 and x0_out.is_contiguous()
+                                   and x0_out.numel() == n):
+        raise RuntimeError("sampler_step_dev: `x0_out` must be a contiguous float32 device tensor of x.numel() elements")
+    if (grad is None) != (grad_scale is None):
+        raise ValueError("sampler_step_dev: `grad` and `grad_scale` go together")
+    if grad is not None:
+        grad, grad_scale = _dev(grad, "grad"), _dev(grad_scale, "grad_scale")
+        rows = x.shape[0] if x.dim() else 1
+        if grad.shape != x.shape or tuple(grad_scale.shape) != (rows,):
+            raise RuntimeError(f"sampler_step_dev: `grad` must be shaped like x and `grad_scale` be [{rows}]")
+        _launch("skp_sampler_step_kp_dev_f32", x, m_c, m_u, x0_prev, noise, out, x0_out, n, copies, pred, bool(clip), table, step,
+                steps, grad, grad_scale, rows)
+        return out
+    _launch("skp_sampler_step_dev_f32", x, m_c, m_u, x0_prev, noise, out, x0_out, n, copies, pred, bool(clip), table, step, steps)
+    return out
+
+
 def image_u8_nhwc(x):
     """float [B,3,H,W] in [0, 1] -> uint8 [B,H,W,3] = (x.permute(0, 2, 3, 1) * 255) truncated, on the device
     (csrc/skp_conv_out.hip; `ptp_utils.latent2image`)."""

@@ -689,6 +689,280 @@ def _reproducible_library_convolutions():
         torch.backends.cudnn.deterministic = prev
 
 
+# ---------------------------------------------------------------------------------------------
+# the captured sampling loop: one recorded step, replayed            text2image_ldm_stable(capture=True)
+# ---------------------------------------------------------------------------------------------
+GRAPH_WARMUP_STEPS = 2         # steps of a captured call that run on eager launches first
+GRAPH_MIN_ROWS = 64            # per-step buffers (table, sinusoids, noise, trace) hold at least this many steps
+
+
+def sample_graph_key(*, rows, doubled, two_forward, tokens, latent_shape, prediction, clip, kind, history, noise, keypoints,
+                     layers, extra=(), tag=()):
+    """Everything shape-like or compiled into a recorded sampling step, as one hashable value: image rows, whether the UNet input
+    is kept doubled, whether guidance takes two forwards, the token counts (conditional, unconditional or None), the latent
+    shape [C, h, w], the prediction type, the clamp, the kind of plan ("axpby" / "ddim_step": the call without a sampler;
+    otherwise the sampler's name), whether an x0 history and per-step noise exist, K of the keypoints (0: none), the stored
+    layers the energy reads, `extra` (the energy's sigma and normalisation, which are arguments of recorded launches) and,
+    last, `tag`: `ops.frozen_tag` over the UNet's parameters, so a weight changed in place is another key."""
+    return (int(rows), bool(doubled), bool(two_forward), tuple(None if t is None else int(t) for t in tokens),
+            tuple(int(v) for v in latent_shape), str(prediction), bool(clip), str(kind), bool(history), bool(noise), int(keypoints),
+            tuple(int(v) for v in layers), tuple(extra), tuple(tag))
+
+
+class SampleGraphs:
+    """The recorded sampling steps of one model, kept on it (`sample_graphs(model)`): `sample_graph_key` -> the recorded step with
+    its static buffers, or "eager" for a key whose recording failed.  A key that differs from a new one in its tag alone (the
+    weights changed) or whose buffers are too short for the call's steps is dropped when the new one is recorded.  `hits` /
+    `misses` count the calls that found / had to record their step; `last` is "hit", "miss" or "eager" for the latest captured
+    call and `last_key` its key.  `clear()` frees the graphs with their private memory pools and buffers."""
+
+    def __init__(self):
+        self.entries, self.hits, self.misses, self.last, self.last_key = {}, 0, 0, None, None
+
+    def clear(self):
+        self.entries.clear()
+        self.last = self.last_key = None
+
+    def keys(self):
+        return list(self.entries)
+
+
+def sample_graphs(model) -> SampleGraphs:
+    return model.__dict__.setdefault("_skp_sample_graphs", SampleGraphs())
+
+
+class _RecordedStep:
+    """Static buffers of one key and the graphs recorded over them: "plain" (the forward(s) of `_predict`, the device-row step
+    kernel, the counter's increment) and, with keypoints, "kp" (`_energy_grad`'s forward and backward in front of the same)."""
+
+    def __init__(self, model, key, latents, context, x0_hist, noise, targets, steps, kind, prediction, clip, sigma, normalize,
+                 layers):
+        dev, n = latents.device, key[0]
+        self.model, self.rows, self.doubled = model, n, key[1]
+        self.kind, self.prediction, self.clip, self.sigma, self.normalize, self.layers = kind, prediction, clip, sigma, normalize, layers
+        self.cap = cap = max(int(steps), GRAPH_MIN_ROWS)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.lat = torch.empty_like(latents)
+        self.uncond = None if context[0] is None else torch.empty_like(context[0])
+        self.cond = torch.empty_like(context[1])
+        self.table = torch.zeros(cap, ops.STEP_ROW, **f32)
+        self.tsin = torch.zeros(cap, int(model.unet._t_dim), **f32)
+        self.counter = torch.zeros(1, device=dev, dtype=torch.int32)
+        first = latents[:n]
+        self.hist = None if x0_hist is None else torch.empty_like(first)
+        self.noise = None if noise is None else torch.zeros((cap,) + tuple(first.shape), **f32)
+        self.targets = self.kscale = self.trace = None
+        if targets is not None:
+            self.targets = KeypointTargets(torch.empty_like(targets.pos), list(targets.ids), torch.empty_like(targets.sel),
+                                           torch.empty_like(targets.tokrow))
+            self.kscale = torch.zeros(cap, **f32)
+            self.trace = torch.zeros(cap, n, **f32)
+        self.graphs = {}                                         # "plain" / "kp" -> (graph, held values, route notes of one replay)
+
+    def stage(self, latents, context, table, timesteps, noise, x0_hist, targets, kscale, at):
+        """This call's values into the static buffers, and the counter to step `at`.  Everything a replay reads is here afterwards."""
+        steps = table.shape[0]
+        self.lat.copy_(latents)
+        if self.uncond is not None:
+            self.uncond.copy_(context[0])
+        self.cond.copy_(context[1])
+        self.table[:steps].copy_(table)
+        # timestep_embedding is elementwise: row i has the bits of the eager call at step i
+        from .ldm.unet import timestep_embedding
+        self.tsin[:steps].copy_(timestep_embedding(timesteps.reshape(-1).to(self.lat.device), self.tsin.shape[1]))
+        self.counter.fill_(int(at))
+        if self.noise is not None:
+            self.noise[:steps].copy_(noise)
+        if self.hist is not None:
+            self.hist.copy_(x0_hist)
+        if self.targets is not None:
+            self.targets.pos.copy_(targets.pos)
+            self.targets.sel.copy_(targets.sel)
+            self.targets.tokrow.copy_(targets.tokrow)
+            self.targets.ids[:] = targets.ids
+            self.kscale[:steps].copy_(kscale)
+
+    @contextlib.contextmanager
+    def _time_rows(self):
+        """Inside the block the UNet's time path is the recorded one: the sinusoid row of the step the device counter names, from
+        the per-call table, through the `time_embedding` MLP (and SDXL's micro-conditioning) as `UNet2DConditionModel.time_path`
+        runs them -- `timestep` is not looked at.  The two Linear layers are plumbing, not a route."""
+        unet = self.model.unet
+        had = "time_path" in unet.__dict__
+        prev = unet.__dict__.get("time_path")
+
+        def time_path(sample, timestep, added_cond_kwargs=None):
+            row = self.tsin.index_select(0, self.counter)
+            temb = unet.time_embedding(row.expand(sample.shape[0], -1).contiguous().to(sample.dtype))
+            if unet.add_embedding is not None:
+                from .ldm.unet import timestep_embedding
+                cond = added_cond_kwargs if added_cond_kwargs is not None else unet.default_added_cond(sample)
+                ids = cond["time_ids"]
+                tids = timestep_embedding(ids.reshape(-1), unet._add_t_dim).reshape(ids.shape[0], -1)
+                temb = temb + unet.add_embedding(torch.cat([cond["text_embeds"], tids.to(sample.dtype)], dim=-1))
+            return temb
+        unet.__dict__["time_path"] = time_path
+        try:
+            yield
+        finally:
+            if had:
+                unet.__dict__["time_path"] = prev
+            else:
+                del unet.__dict__["time_path"]
+
+    def _step(self, latents, pred_c, pred_u, **kp):
+        """The device-row step kernel of this key's plan, writing the next UNet input (both copies of a doubled one) in place."""
+        row = dict(table=self.table, step=self.counter, steps=self.cap)
+        copies = 2 if self.doubled else 1
+        if self.kind == "axpby":
+            return ops.axpby_dev(latents, pred_c, out=self.lat, **row)
+        if self.kind == "ddim_step":
+            return ops.ddim_step_dev(latents, pred_c, pred_u, prediction=self.prediction, clip=self.clip, copies=copies,
+                                     out=self.lat, **row)
+        routes.note("sample.step", "sampler_step")
+        return ops.sampler_step_dev(latents, pred_c, pred_u, x0_prev=self.hist, noise=self.noise, prediction=self.prediction,
+                                    clip=self.clip, copies=copies, out=self.lat, x0_out=self.hist, **row, **kp)
+
+    def body(self, which):
+        """One step on the static buffers, nothing from the host: what is recorded, and what runs once on eager launches before."""
+        context = [self.uncond, self.cond]
+        with self._time_rows():
+            if which == "kp":
+                pred_c, pred_u, energy, g = _energy_grad(self.model, self.lat, context, None, self.targets, self.sigma, self.layers,
+                                                         doubled=self.doubled)
+                s = self.kscale.index_select(0, self.counter).expand(self.rows)
+                if self.normalize:
+                    s = s / g.pow(2).mean(dim=(1, 2, 3)).sqrt().clamp_min(1e-12)
+                self.trace.index_copy_(0, self.counter.to(torch.int64), energy[None])
+                self._step(self.lat[:self.rows] if self.doubled else self.lat, pred_c, pred_u, grad=g, grad_scale=s)
+            else:
+                latents, pred_c, pred_u = _predict(self.model, self.lat, context, None, self.doubled)
+                self._step(latents, pred_c, pred_u)
+        ops.step_advance(self.counter)
+
+    def record(self, which):
+        """Run the step once on eager launches (the caches of the frozen weights and the library's choices are then those of
+        exactly this body) with the buffers put back afterwards, then record it.  Neither run's route notes stay in the ledger:
+        they come back once per replay."""
+        kept = [(t, t.clone()) for t in (self.lat, self.hist, self.trace, self.counter) if t is not None]
+        before = routes.snapshot()
+        try:
+            self.body(which)
+        finally:
+            routes.merge(routes.delta(before), -1)
+        for t, saved in kept:
+            t.copy_(saved)
+        graph = torch.cuda.CUDAGraph()
+        before = routes.snapshot()
+        try:
+            with ops.recording() as held, torch.cuda.graph(graph):
+                self.body(which)
+        finally:
+            noted = routes.delta(before)
+            routes.merge(noted, -1)
+        self.graphs[which] = (graph, held, noted)
+
+    def replay(self, which):
+        graph, _, noted = self.graphs[which]
+        graph.replay()
+        routes.merge(noted)
+
+
+def _overrides_step_callback(controller) -> bool:
+    return controller is not None and getattr(type(controller), "step_callback", None) is not AttentionControl.step_callback
+
+
+def _default_rows(sched, ts, kind):
+    """The rows of the call without a sampler, from `DDIMScheduler._coefficients` (the timestep table of the call must be set):
+    "axpby" -- cx = pa / sa and ce = pb - pa sb / sa, the two numbers `DDIMScheduler.step` hands `ops.axpby`, formed the same way;
+    "ddim_step" -- c0 = pa and ce = pb."""
+    from .ldm.samplers import StepCoef
+    rows = []
+    for t in ts:
+        sa, sb, pa, pb = sched._coefficients(t)
+        rows.append(StepCoef(sa, sb, pa / sa, pa, pb - pa * sb / sa, 0.0, 0.0) if kind == "axpby" else
+                    StepCoef(sa, sb, 0.0, pa, pb, 0.0, 0.0))
+    return rows
+
+
+def _captured_steps(model, controller, latents, context, ts, at, guidance_scale, plan, coefs, x0_hist, noise, targets, kp, doubled):
+    """Steps `at` .. of the loop of `text2image_ldm_stable(capture=True)` as replays of a recorded step -> the latents after the
+    last step (laid out like `latents`), or None where the call has to go on with eager launches: a controller with its own
+    `step_callback`, the clamped default step (torch ops on host numbers), weights that take gradients, a key marked eager, or a
+    recording that failed just now (one warning, the key marked eager, never retried).  Notes `sample.loop` / `graph` per replay."""
+    import warnings
+    from .ldm.samplers import pack_step_table
+    cache, sched, steps = sample_graphs(model), model.scheduler, len(ts)
+    guided = context[0] is not None
+    n = latents.shape[0] // 2 if doubled else latents.shape[0]
+    if _overrides_step_callback(controller):
+        warnings.warn("text2image_ldm_stable(capture=True): the controller overrides step_callback, which runs on the host after "
+                      "every step; the call stays on eager launches")
+        return None
+    if plan is None:
+        prediction, clip = sched.prediction_type, bool(sched.clip_sample)
+        kind = "axpby" if prediction == "epsilon" and not guided else "ddim_step"
+        if kind == "axpby" and clip:
+            warnings.warn("text2image_ldm_stable(capture=True): the clamped default step is torch arithmetic on host numbers; the "
+                          "call stays on eager launches")
+            return None
+        coefs = _default_rows(sched, ts, kind)
+    else:
+        prediction, clip, kind = plan.prediction_type, bool(plan.clip_sample), plan.kind
+    tag = ops.frozen_tag(list(model.unet.parameters()))
+    if tag is None:
+        warnings.warn("text2image_ldm_stable(capture=True): the UNet has parameters that take gradients; the call stays on eager "
+                      "launches")
+        return None
+    layers, extra, needs = (0, 1, 2, 3), (), ["plain"] * steps
+    if targets is not None:
+        lo, hi, kscale, sigma, normalize, trace = kp
+        extra = (float(sigma), bool(normalize))
+        needs = ["kp" if lo <= i / steps < hi else "plain" for i in range(steps)]
+    key = sample_graph_key(rows=n, doubled=doubled, two_forward=guided and not doubled,
+                           tokens=(context[1].shape[1], context[0].shape[1] if guided else None), latent_shape=latents.shape[1:],
+                           prediction=prediction, clip=clip, kind=kind, history=x0_hist is not None, noise=noise is not None,
+                           keypoints=0 if targets is None else len(targets.ids), layers=layers, extra=extra, tag=tag)
+    hit, cache.last_key = cache.entries.get(key), key
+    if hit == "eager":
+        cache.last = "eager"
+        return None
+    if hit is None or hit.cap < steps:
+        for k in [k for k in cache.entries if k[:-1] == key[:-1]]:
+            del cache.entries[k]                                 # changed weights or a longer table: the graph and what it holds retire
+        hit = None
+    try:
+        step = hit if hit is not None else _RecordedStep(model, key, latents, context, x0_hist, noise, targets, steps, kind,
+                                                            prediction, clip, extra[0] if extra else 0.0,
+                                                            extra[1] if extra else False, layers)
+        ks = None if targets is None else torch.tensor([float(kscale) * c.sb for c in coefs], dtype=torch.float64).to(torch.float32)
+        step.stage(latents, context, pack_step_table(coefs, guidance_scale), torch.as_tensor(ts), noise, x0_hist, targets, ks, at)
+        missing = [w for w in sorted(set(needs[at:])) if w not in step.graphs]
+        for which in missing:
+            step.record(which)
+    except Exception as e:                                       # noqa: BLE001 -- capture is an optimisation of the host side only
+        warnings.warn(f"text2image_ldm_stable(capture=True): the call stays on eager launches (recording the step failed: {e})")
+        hooked = model.unet.__dict__.get("_skp_hook_controller")
+        if hooked is not None and hasattr(hooked, "reset"):
+            hooked.reset()
+        cache.entries[key], cache.last = "eager", "eager"
+        return None
+    cache.entries[key] = step
+    if missing:
+        cache.misses, cache.last = cache.misses + 1, "miss"
+    else:
+        cache.hits, cache.last = cache.hits + 1, "hit"
+    for i in range(at, steps):                                   # back to back: no copy, no read-back, no synchronisation
+        step.replay(needs[i])
+        routes.note("sample.loop", "graph")
+        if controller is not None:
+            controller.reset()
+    if targets is not None and trace is not None:
+        rows = step.trace[:steps].clone()
+        trace.extend(rows[i] for i in range(at, steps) if needs[i] == "kp")
+    return step.lat.clone()
+
+
 @torch.no_grad()
 def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                           generator: Optional[torch.Generator] = None, latent: Optional[torch.Tensor] = None, *,
@@ -696,7 +970,7 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                           uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None,
                           sampler: Optional[str] = None, eta: float = 0.0, keypoints=None, keypoint_indices=None,
                           keypoint_scale: float = 2.0, keypoint_sigma: float = 2.0, keypoint_steps=(0.0, 1.0),
-                          keypoint_normalize: bool = True, keypoint_trace: Optional[list] = None):
+                          keypoint_normalize: bool = True, keypoint_trace: Optional[list] = None, capture: bool = False):
     """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` steps of `sampler`
     (deterministic DDIM by default) and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
@@ -739,7 +1013,16 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     tried on the seeded reduced-width tree of the tests, never on trained weights.  ValueError: one of the two without the other,
     a shape mismatch, an index outside the embedding (or twice).  Without `keypoints` nothing changes: the same routes, the same
     bits.
-    The loop is not captured into a graph.  NOT reproduced: `register_attention_control_generation`, which re-installs the
+    `capture=True` (keyword-only extension; off by default, and then every route, bit and ledger note is what it was): on a float32
+    GPU model the first two steps run as always, then ONE step is recorded as a graph over static buffers and replayed for every
+    remaining step with no host work in between -- the per-step scalars, the timestep's sinusoid row, the noise row and the
+    keypoint scale are read from device tables by a device counter (include/skp_sampler_graph.h, `ops.sampler_step_dev`), so the
+    replays compute what the eager launches compute, bit for bit.  With keypoints the guided step is a second graph over the same
+    buffers and the host picks one per step.  Graphs and buffers are kept on the model (`sample_graphs(model)`, with `clear()`),
+    keyed by `sample_graph_key` and the frozen tag of the UNet's weights; a later call with the same key refreshes the buffers and
+    replays.  Calls of fewer than three steps, a controller with its own `step_callback` (one warning), the clamped default step
+    and a key whose recording failed (one warning, never retried) stay on eager launches; host tensors take the host route.
+    The ledger site `sample.loop` says per step which it was: "graph", "eager" or "host".  NOT reproduced: `register_attention_control_generation`, which re-installs the
     attention math the module tree already computes.  `height`,
     `width` and `output_type` are keyword-only extensions (the reference fixes 512 x 512).  The scheduler's timestep table is
     restored afterwards, so a sampling call between optimisation steps does not move their noise level.  The model must have
@@ -807,32 +1090,55 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
         first = latents[:n]
         x0_hist = None if plan.kind == "ddim" else torch.empty_like(first)
         noise = _step_noise(plan, len(coefs), first, generator).to(first) if plan.stochastic else None     # one upload
+
+    def eager_step(i, t, latents):
+        """Step i on eager launches (or host tensors): the loop body the call always had."""
+        if plan is not None:
+            kp = {}
+            if targets is not None and lo <= i / len(coefs) < hi:
+                pred_c, pred_u, energy, g = _energy_grad(model, latents, context, t, targets, keypoint_sigma, doubled=doubled)
+                s = torch.full_like(energy, float(keypoint_scale) * coefs[i].sb)
+                if keypoint_normalize:
+                    s = s / g.pow(2).mean(dim=(1, 2, 3)).sqrt().clamp_min(1e-12)
+                if keypoint_trace is not None:
+                    keypoint_trace.append(energy)
+                kp = dict(preds=(pred_c, pred_u), grad=g, grad_scale=s)
+            latents = sampler_latent_step(model, controller, latents, context, t, guidance_scale, plan=plan, coef=coefs[i],
+                                          x0_hist=x0_hist, noise=None if noise is None else noise[i], doubled=doubled, **kp)
+        elif guided:
+            latents = guided_latent_step(model, controller, latents, context, t, guidance_scale, doubled=doubled)
+        else:
+            latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)
+        if controller is not None:
+            controller.reset()
+        return latents
+
     with _reproducible_library_convolutions():                 # the loop and the decode: one call, one result, bit for bit
         try:
             if plan is None:
                 sched.set_timesteps(num_inference_steps)         # (a plan has its own table and leaves the scheduler alone)
+            ts = sched.timesteps if plan is None else timesteps
+            # capture: None (the call as it always was: nothing noted at `sample.loop`), or the route of every step that is not a replay
+            loop_route = None
+            if capture:
+                on_gpu = latents.is_cuda and all(p.is_cuda and p.dtype == torch.float32 for p in model.unet.parameters())
+                loop_route = "eager" if on_gpu else "host"
             with ops.up2_in_unet(latents.is_cuda):
-                for i, t in enumerate(sched.timesteps if plan is None else timesteps):
-                    if plan is not None:
-                        kp = {}
-                        if targets is not None and lo <= i / len(coefs) < hi:
-                            pred_c, pred_u, energy, g = _energy_grad(model, latents, context, t, targets, keypoint_sigma,
-                                                                     doubled=doubled)
-                            s = torch.full_like(energy, float(keypoint_scale) * coefs[i].sb)
-                            if keypoint_normalize:
-                                s = s / g.pow(2).mean(dim=(1, 2, 3)).sqrt().clamp_min(1e-12)
-                            if keypoint_trace is not None:
-                                keypoint_trace.append(energy)
-                            kp = dict(preds=(pred_c, pred_u), grad=g, grad_scale=s)
-                        latents = sampler_latent_step(model, controller, latents, context, t, guidance_scale, plan=plan,
-                                                      coef=coefs[i], x0_hist=x0_hist, noise=None if noise is None else noise[i],
-                                                      doubled=doubled, **kp)
-                    elif guided:
-                        latents = guided_latent_step(model, controller, latents, context, t, guidance_scale, doubled=doubled)
-                    else:
-                        latents = latent_step(model, controller, latents, context, t, guidance_scale, low_resource=True)
-                    if controller is not None:
-                        controller.reset()
+                wants_graph = loop_route == "eager" and len(ts) > GRAPH_WARMUP_STEPS
+                for i, t in enumerate(ts):
+                    if wants_graph and i == GRAPH_WARMUP_STEPS:
+                        done = _captured_steps(model, controller, latents, context, ts, i, guidance_scale, plan,
+                                               None if plan is None else coefs, x0_hist if plan is not None else None,
+                                               noise if plan is not None else None, targets,
+                                               (lo, hi, keypoint_scale, keypoint_sigma, keypoint_normalize, keypoint_trace)
+                                               if targets is not None else None, doubled)
+                        if done is not None:
+                            latents = done
+                            break
+                        wants_graph = False
+                    latents = eager_step(i, t, latents)
+                    if loop_route is not None:
+                        routes.note("sample.loop", loop_route)
         finally:
             sched.timesteps, sched.num_inference_steps = kept
         if doubled:

@@ -72,6 +72,10 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # the step of a named sampler (ptp_utils.sampler_latent_step; text2image_ldm_stable(sampler=) other than the eta = 0 DDIM
     # step it always had, which has no gate and notes nothing): the fused step kernel / the formula in torch on host tensors
     "sample.step": {"sampler_step": "hip", "host": "host"},
+    # text2image_ldm_stable(capture=True), once per step: a replay of the recorded step (its gates' own notes are merged per replay)
+    # / the step on eager launches (the warm-up steps, and calls that cannot be recorded) / host tensors.  A call without
+    # `capture` notes nothing here.
+    "sample.loop": {"graph": "hip", "eager": "eager", "host": "host"},
     # energy and latent gradient of keypoint guidance (ptp_utils.keypoint_energy_grad): the fused maps + point-loss node
     # (ops.MapPointLossFn; its map kernels note `map.fwd` / `map.bwd` as well) / torch ops on host tensors and other dtypes
     "sample.keypoints": {"map_point_loss": "hip", "host": "host"},

@@ -4,6 +4,7 @@ classifier-free guidance, and print the route table of one guided step.
 
     python tools/generate_bench.py [--model synthetic-sd15] [--size 512] [--steps 10] [--n 4] [--rounds 3] [--tokens 77] [--json FILE]
                                    [--sampler ddim|dpm++2m|dpm++2m-sde [--eta 0] [--sampler-steps K]] [--variants A,G1] [--keypoints]
+                                   [--capture]
 
 Every timed call ends in a device synchronise (the uint8 image is copied to the host); every shape is warmed up once before the
 timed rounds; the variants run alternately inside each round, so a drift of the machine shows up as spread, not as a difference.
@@ -19,6 +20,10 @@ drawn from the seed, every step guided), in turn with the call without it (with 
 timed against the route the package had before it -- dense fused maps under autograd, a gather, torch ops for the target and the
 MSE -- on the hooked layers of SD-1.5 at 512^2 (sides 16, 16, 16, 32; 8 heads of 160, 160, 160, 80 channels; R = 128) with
 T = 77 and T = 500 tokens, K = 10, n = 1 and 4 rows.
+`--capture`: every variant (those of the other flags included) is timed a second time as `<variant>+graph`, the same call with
+`capture=True` -- two steps on eager launches, the rest as replays of one recorded step -- in turn with the eager call; the
+warm-up call of each variant is timed too and printed as `first call`: for a `+graph` variant it holds the one-off cost of
+recording (a dry run of the step, the capture, the graph's instantiation), which later calls with the same key do not pay.
 Times are per image."""
 import argparse
 import json
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--sampler-steps", type=int, default=None)
     ap.add_argument("--variants", default=None)
     ap.add_argument("--keypoints", action="store_true")
+    ap.add_argument("--capture", action="store_true")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "generate_bench.py measures the GPU path only"
@@ -92,13 +98,19 @@ def main():
         kp_ids = torch.randperm(a.tokens, generator=g)[:10].sort().values
         kp = dict(keypoints=torch.rand(len(kp_ids), 2, generator=g), keypoint_indices=kp_ids)
         overs = {name: o for suffix, over in overs.items() for name, o in ((suffix, over), (suffix + "+kp", {**over, **kp}))}
+    if a.capture:
+        overs = {name: o for suffix, over in overs.items() for name, o in ((suffix, over), (suffix + "+graph", {**over, "capture": True}))}
     made = {suffix: make(**over) for suffix, over in overs.items()}
     variants = {k + suffix: made[suffix][k] for k in names for suffix in overs}
     width = max([7] + [len(k) for k in variants])
     times = {k: [] for k in variants}
-    for k, fn in variants.items():                              # warm-up: every shape once
+    first = {}
+    for k, fn in variants.items():                              # warm-up: every shape once (a +graph variant records its step here)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
         fn()
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        first[k] = time.perf_counter() - t0
     for _ in range(a.rounds):
         for k, fn in variants.items():
             torch.cuda.synchronize()
@@ -109,6 +121,11 @@ def main():
     print(f"{a.model} at {a.size}^2, {a.steps} steps, n = {a.n}, {a.tokens} tokens, {a.rounds} rounds; seconds per image")
     for k, ts in times.items():
         print(f"  {k:{width}s} median {sorted(ts)[len(ts) // 2]:.4f}   min {min(ts):.4f}   max {max(ts):.4f}   all {[round(t, 4) for t in ts]}")
+    if a.capture:
+        print("first call of each variant, seconds for the whole call (all its images; caches, library choices and, for +graph, the "
+              "recording):\n  " + "   ".join(f"{k} {v:.3f}" for k, v in first.items()))
+        cache = ptp_utils.sample_graphs(ldm)
+        print(f"recorded steps kept on the model: {len(cache.keys())} keys, {cache.hits} hits, {cache.misses} misses")
     # routes of ONE guided step (2 rows) and of one guided step of n images (2n rows)
     tables = {}
     t = ldm.scheduler.timesteps[0]
@@ -123,7 +140,7 @@ def main():
     node = node_against_older_route(a.rounds) if a.keypoints else {}
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(args=vars(a), seconds_per_image=times, routes={str(k): v for k, v in tables.items()},
+            json.dump(dict(args=vars(a), seconds_per_image=times, first_call_seconds=first, routes={str(k): v for k, v in tables.items()},
                            map_point_loss_seconds=node), f, indent=1)
 
 

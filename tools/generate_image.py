@@ -6,7 +6,7 @@
                                    [--uncond unc.pt | --negative-prompt TEXT] [--guidance 7.5] [--batch 1] [--prediction-type epsilon|v_prediction|sample]
                                    [--sampler ddim|dpm++2m|dpm++2m-sde] [--eta 0]
                                    [--keypoints "r,c;r,c;..."|FILE.pt --keypoint-indices FILE.pt|"i,j,..." [--keypoint-scale 2]
-                                    [--keypoint-sigma 2] [--keypoint-steps 0,1]]
+                                    [--keypoint-sigma 2] [--keypoint-steps 0,1]] [--capture]
 
 `--embedding`: a tensor [1, T, D] (or [T, D]) saved with torch.save -- what `optimize_embedding` returns.  Image i is sampled from
 seed + i and written to `<out>_<i>.png` when PIL imports, else to `<out>_<i>.npy` (uint8 [H, W, 3]).
@@ -24,7 +24,9 @@ the stochastic ones draw their noise from the image's seed, after its starting n
 tensor [K, 2] saved with torch.save (the same targets for every image), for K token ids of the embedding, written out or the
 tensor `find_best_indices` returned (the reference's outputs/indices.pt); `--keypoint-scale`, `--keypoint-sigma` (map pixels) and
 `--keypoint-steps lo,hi` (the guided fraction of the steps) as in `text2image_ldm_stable`.  Prints each image's energy at the first
-and at the last guided step.  The default scale was only tried on the seeded reduced-width tree, never on trained weights."""
+and at the last guided step.  The default scale was only tried on the seeded reduced-width tree, never on trained weights.
+`--capture` (off by default): `text2image_ldm_stable(capture=True)` -- after two steps on eager launches the rest of every call
+replays one recorded step; the images are the same, bit for bit, and calls after the first reuse the recording."""
 import argparse
 import os
 import sys
@@ -56,6 +58,7 @@ def main():
     ap.add_argument("--keypoint-scale", type=float, default=2.0)
     ap.add_argument("--keypoint-sigma", type=float, default=2.0)
     ap.add_argument("--keypoint-steps", default="0,1")
+    ap.add_argument("--capture", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -117,7 +120,7 @@ def main():
         image, _ = ptp_utils.text2image_ldm_stable(ldm, emb, controller, num_inference_steps=a.steps, guidance_scale=a.guidance,
                                                    generator=gens[0] if a.batch == 1 else gens, height=a.size, width=a.size,
                                                    uncond_embedding=unc, uncond_prompt=a.negative_prompt, sampler=a.sampler, eta=a.eta,
-                                                   keypoint_trace=trace, **kp)
+                                                   keypoint_trace=trace, capture=a.capture, **kp)
         for row, i in enumerate(ids):
             if trace:
                 print(f"image {i}: keypoint energy {float(trace[0][row]):.6f} at the first guided step, {float(trace[-1][row]):.6f} "
