@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- MUST precede the dlopen below: libskp_hip.so has 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SKP_LIB_PATH: another BUILD of the same library (same-box A/B of two kernel versions, tools/ab_build.py); never a fallback
 LIB_PATH = os.environ.get("SKP_LIB_PATH") or os.path.join(_HERE, "csrc", "libskp_hip.so")
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
@@ -185,9 +185,16 @@ SAMPLER_GRAPH_SIGNATURES = {
 }
 
 
+# include/skp_targets.h, held to it the same way (tests/test_pose_transfer_host.py): the energy of pose transfer, maps against maps
+TARGET_SIGNATURES = {
+    "skp_map_target_loss_workspace": [_i, _i, _i, _i],
+    "skp_map_target_loss_f32": [_pf, _pf, _i, _i, _i, _i, _i, _pf, _pf, _vp, _vp],
+}
+
+
 def signature(name):
-    """argtypes of an entry of any of the five headers."""
-    for table in (SIGNATURES, KEYPOINT_SIGNATURES, OVERLAY_SIGNATURES, SAMPLER_GRAPH_SIGNATURES):
+    """argtypes of an entry of any of the six headers."""
+    for table in (SIGNATURES, KEYPOINT_SIGNATURES, OVERLAY_SIGNATURES, SAMPLER_GRAPH_SIGNATURES, TARGET_SIGNATURES):
         if name in table:
             return table[name]
     return LOCATE_SIGNATURES[name]
@@ -215,7 +222,7 @@ def lib():
             "(or `make -C stablekeypoints_amd/csrc`). There is no CPU/eager fallback for the hot path.")
     l = C.CDLL(LIB_PATH)
     for name, argtypes in (*SIGNATURES.items(), *KEYPOINT_SIGNATURES.items(), *OVERLAY_SIGNATURES.items(),
-                           *LOCATE_SIGNATURES.items(), *SAMPLER_GRAPH_SIGNATURES.items()):
+                           *LOCATE_SIGNATURES.items(), *SAMPLER_GRAPH_SIGNATURES.items(), *TARGET_SIGNATURES.items()):
         if not hasattr(l, name):
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(l, name)

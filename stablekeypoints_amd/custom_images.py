@@ -20,10 +20,15 @@ class CustomDataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.files)
 
-    def __getitem__(self, i):
+    @staticmethod
+    def load_image(path, image_size=512):
+        """One image file -> float32 [3, image_size, image_size] in [0, 1]: the resize every item of the dataset goes through."""
         from PIL import Image
-        img = Image.open(self.files[i]).convert("RGB").resize((self.size, self.size), Image.BILINEAR)
-        return {"img": torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()}
+        img = Image.open(path).convert("RGB").resize((image_size, image_size), Image.BILINEAR)
+        return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()
+
+    def __getitem__(self, i):
+        return {"img": self.load_image(self.files[i], self.size)}
 
 
 class AnnotatedImages(CustomDataset):

@@ -662,6 +662,47 @@ def point_loss(M, pos, sigma: float):
     return partial.sum(dim=(1, 2)) / float(K * R * R), G
 
 
+TARGET_MODES = {"mse": 0, "cosine": 1}      # the `mode` of include/skp_targets.h by the name `text2image_ldm_stable(target_energy=)` takes
+
+
+def map_target_loss(M, target, mode):
+    """Energy of K maps per image against K target maps (csrc/skp_target_loss.hip, formulas in include/skp_targets.h): M [B,K,R,R],
+    target [B,K,R,R] or [1,K,R,R] (one target for every image, read in place), on the device; `mode` "mse" -- E[b] = mean_{k,r,c}
+    (M - T)^2 -- or "cosine" -- E[b] = (1/K) sum_k (1 - cos(M_k, T_k)), a map of zeros counting 1 -> (E [B], G [B,K,R,R] = dE[b] /
+    dM[b]).  No autograd; one or two kernels and one fixed-order sum of their chunk sums: the same bits from call to call."""
+    if mode not in TARGET_MODES:
+        raise ValueError(f"map_target_loss: mode must be one of {sorted(TARGET_MODES)}, got {mode!r}")
+    M, target = _dev(M.detach(), "M"), _dev(target.detach(), "target")
+    if M.dim() != 4 or M.shape[2] != M.shape[3] or target.dim() != 4 or target.shape[0] not in (1, M.shape[0]) \
+            or tuple(target.shape[1:]) != tuple(M.shape[1:]):
+        raise RuntimeError(f"map_target_loss: maps {tuple(M.shape)} must be [B,K,R,R] and targets {tuple(target.shape)} [B,K,R,R] "
+                           "or [1,K,R,R]")
+    B, K, R, _ = M.shape
+    code = TARGET_MODES[mode]
+    partial = torch.empty(B, K, (R * R + 1023) // 1024, device=M.device, dtype=torch.float32)
+    G = torch.empty_like(M)
+    ws = _workspace("skp_map_target_loss_workspace", B, K, R, code, device=M.device)
+    _launch("skp_map_target_loss_f32", M, target, B, target.shape[0], K, R, code, partial, G, ws)
+    return partial.sum(dim=(1, 2)) / (float(K * R * R) if code == 0 else float(2 * K)), G
+
+
+def _k_row_maps(st, sel, tokrow):
+    """(S, M [B,K,R,R], lse) of a stack for the K tokens `sel`: the K rows alone where the wide kernel serves the shape, else all
+    rows and a gather."""
+    if map_wide_supported(st.T, st.R, st.sides):
+        return st.maps(tokrow=tokrow, n_rows=sel.shape[0])
+    S, M, lse = st.maps()
+    return S, M.index_select(1, sel), lse
+
+
+def _k_row_backward(ctx, go):
+    """The backward of an energy of K rows per batch row whose forward saved (sel, G): G scaled by the incoming gradient, through
+    `_stack_grads(rows=...)`."""
+    st, S, lse, (sel, G) = _saved_stack(ctx)
+    rows = (sel.expand(st.B, sel.shape[0]), go.reshape(st.B, 1, 1, 1).float() * G)
+    return (None, *_stack_grads(st, S, lse, ctx.needs_input_grad[1:], rows=rows))
+
+
 class MapPointLossFn(torch.autograd.Function):
     """One node for `maps of K tokens -> energy against caller-given positions` (keypoint guidance of image sampling,
     ptp_utils.keypoint_energy_grad), the sibling of MapLossesFn: the map backward sees K rows per batch row, not a dense [B,T,R,R].
@@ -679,20 +720,34 @@ class MapPointLossFn(torch.autograd.Function):
         K = sel.shape[0]
         if tuple(pos.shape) != (st.B, K, 2) or tuple(tokrow.shape) != (st.T,):
             raise RuntimeError("MapPointLossFn: positions [B,K,2] and a row table of T tokens")
-        if map_wide_supported(st.T, st.R, st.sides):
-            S, M, lse = st.maps(tokrow=tokrow, n_rows=K)
-        else:
-            S, M, lse = st.maps()
-            M = M.index_select(1, sel)
+        S, M, lse = _k_row_maps(st, sel, tokrow)
         E, G = point_loss(M, pos, float(meta["sigma"]))
         _save_stack(ctx, st, S, lse, sel, G)
         return E
 
+    backward = staticmethod(_k_row_backward)
+
+
+class MapTargetLossFn(torch.autograd.Function):
+    """MapPointLossFn against target MAPS (pose transfer, ptp_utils.keypoint_energy_grad with `MapTargets`): the same forward up to
+    the K rows' maps, `map_target_loss` for the energy and its unit gradient, the same backward.
+    apply(meta, q_0, k_0, q_1, k_1, ...); meta = dict(R, heads, scales, target [B,K,R,R] or [1,K,R,R] float32 on the device, mode
+    "mse" / "cosine", sel, tokrow as there).  Returns E [B]."""
+
     @staticmethod
-    def backward(ctx, go):
-        st, S, lse, (sel, G) = _saved_stack(ctx)
-        rows = (sel.expand(st.B, sel.shape[0]), go.reshape(st.B, 1, 1, 1).float() * G)
-        return (None, *_stack_grads(st, S, lse, ctx.needs_input_grad[1:], rows=rows))
+    def forward(ctx, meta, *qk: torch.Tensor):
+        st = MapStack.of_flat("MapTargetLossFn", qk, meta["heads"], meta["scales"], meta["R"])
+        sel, target, tokrow = meta["sel"], meta["target"], meta["tokrow"]
+        K = sel.shape[0]
+        if target.dim() != 4 or target.shape[0] not in (1, st.B) or tuple(target.shape[1:]) != (K, st.R, st.R) \
+                or tuple(tokrow.shape) != (st.T,):
+            raise RuntimeError("MapTargetLossFn: targets [B,K,R,R] or [1,K,R,R] and a row table of T tokens")
+        S, M, lse = _k_row_maps(st, sel, tokrow)
+        E, G = map_target_loss(M, target, meta["mode"])
+        _save_stack(ctx, st, S, lse, sel, G)
+        return E
+
+    backward = staticmethod(_k_row_backward)
 
 
 UNWARP_MAX_K = 32

@@ -6,7 +6,8 @@ Kept names/signatures: `AttentionControl`, `AttentionStore`,
 `latent2image`, `init_latent`, `latent_step`, `text2image_ldm_stable` (ptp_utils.py:307-349,420-461); `init_latents` and
 `guided_latent_step` are this port's batched / classifier-free-guidance companions of the last two, `sampler_latent_step` the step
 of the named samplers (ldm/samplers.py), `keypoint_energy_grad` the energy and latent gradient of keypoint guidance
-(`text2image_ldm_stable(keypoints=...)`).
+(`text2image_ldm_stable(keypoints=...)`), `pose_targets` / `gaussian_target_maps` the target maps of pose transfer
+(`text2image_ldm_stable(target_maps=...)`).
 
 What changes under the hood
   * the hooked cross-attention does NOT up-sample the layer input, re-project it and materialise a
@@ -264,6 +265,7 @@ def register_attention_control(model, controller, feature_upsample_res=256):
             cross_att_count += register_recr(child, 0, "up")
     controller.num_att_layers = cross_att_count
     model.__dict__["_skp_hook_controller"] = controller        # (the sampling loop empties the hooked store after every forward)
+    model.__dict__["_skp_hook_res"] = int(feature_upsample_res)     # R of the stored maps (pose transfer resamples its targets to it)
     assert cross_att_count != 0, ("No cross attention layers found in the model. The module tree must use the "
                                   "diffusers==0.8.0 `CrossAttention` layout.")
 
@@ -490,7 +492,131 @@ def _keypoint_targets(pos, ids, n, T, device):
     return KeypointTargets(pos.to(device).contiguous(), ids, torch.tensor(ids, dtype=torch.int64).to(device), tokrow.to(device))
 
 
-def keypoint_energy_grad(model, latents, context, t, keypoints, indices, sigma, layers=(0, 1, 2, 3), doubled=False):
+TARGET_ENERGIES = ("cosine", "mse")
+
+
+class MapTargets(NamedTuple):
+    """The checked arguments of pose transfer -- keypoint guidance toward target maps -- on the device, made once per call
+    (`_map_targets`); the counterpart of `KeypointTargets`."""
+    maps: torch.Tensor                       # [n, K, R, R] or [1, K, R, R] (one target for every image), in the latents' dtype
+    mode: str                                # "cosine" or "mse"
+    ids: list                                # the K token ids, host ints
+    sel: torch.Tensor                        # the same, int64 [K] on the device
+    tokrow: torch.Tensor                     # int32 [T] on the device: the map row of a token, -1 for the others
+
+
+def _target_map_ids(target_maps, target_energy, keypoint_indices, T):
+    """Everything about target maps that does not depend on the number of images -> (maps [m, K, R', R'] where they are, ids: K
+    host ints).  ValueError for maps without token ids, an unknown energy, maps that are not [K, R', R'] or [m, K, R', R'] with
+    square R' and K = the number of ids, an index outside the T tokens or listed twice."""
+    if target_maps is None or keypoint_indices is None:
+        raise ValueError("target_maps and keypoint_indices go together: K target maps for K token ids")
+    if target_energy not in TARGET_ENERGIES:
+        raise ValueError(f"target_energy must be one of {TARGET_ENERGIES}, got {target_energy!r}")
+    ids = [int(v) for v in torch.as_tensor(keypoint_indices).reshape(-1).tolist()]
+    maps = torch.as_tensor(target_maps).detach()
+    if maps.dim() == 3:
+        maps = maps[None]
+    if maps.dim() != 4 or not ids or maps.shape[1] != len(ids) or maps.shape[2] != maps.shape[3] or not maps.is_floating_point() \
+            or 0 in maps.shape:
+        raise ValueError(f"target_maps {tuple(maps.shape)} must be floating [K, R, R] or [n, K, R, R] with K = {len(ids)} token ids")
+    if min(ids) < 0 or max(ids) >= T:
+        raise ValueError(f"keypoint_indices {ids} reach outside the embedding's {T} tokens")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"keypoint_indices {ids} must be distinct")
+    return maps, ids
+
+
+def resample_target_maps(maps, R):
+    """Target maps [m, K, R', R'] at the resolution R of the model's stored maps: as they are for R' == R, otherwise ONE library
+    call, torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True) -- plumbing of the sampling call
+    (once per call), not a route."""
+    if maps.shape[-1] == R and maps.shape[-2] == R:
+        return maps
+    import torch.nn.functional as F
+    return F.interpolate(maps, size=(R, R), mode="bilinear", align_corners=False, antialias=True)
+
+
+def _map_targets(maps, ids, mode, n, T, R, device, dtype):
+    """(maps, ids) of `_target_map_ids` for n images of a model whose maps are R x R -> MapTargets; ValueError when the maps are
+    neither one row nor n."""
+    if maps.shape[0] not in (1, n):
+        raise ValueError(f"target_maps {tuple(maps.shape)}: {maps.shape[0]} rows of targets for {n} images")
+    maps = resample_target_maps(maps.to(device=device, dtype=dtype), int(R)).contiguous()
+    tokrow = torch.full((T,), -1, dtype=torch.int32)
+    tokrow[ids] = torch.arange(len(ids), dtype=torch.int32)
+    return MapTargets(maps, mode, ids, torch.tensor(ids, dtype=torch.int64).to(device), tokrow.to(device))
+
+
+def map_target_energy(M, target, mode):
+    """The two energies of include/skp_targets.h in torch ops, in the dtype of M and differentiable by it: M [n, K, R, R], target
+    [n, K, R, R] or [1, K, R, R] -> E [n].  "mse": mean_{k,r,c} (M - T)^2.  "cosine": (1/K) sum_k 1/2 sum (M / |M| - T / |T|)^2 =
+    (1/K) sum_k (1 - cos(M_k, T_k)), formed from the squared differences; a map or target of zeros counts E_k = 1 and takes no
+    gradient."""
+    T = target.to(M.dtype).expand_as(M)
+    if mode == "mse":
+        return ((M - T) ** 2).mean(dim=(1, 2, 3))
+    if mode != "cosine":
+        raise ValueError(f"target_energy must be one of {TARGET_ENERGIES}, got {mode!r}")
+    a, c = (M * M).sum(dim=(2, 3), keepdim=True), (T * T).sum(dim=(2, 3), keepdim=True)
+    ok = (a > 0) & (c > 0)
+    one = torch.ones_like(a)
+    diff = M * torch.where(ok, a, one).rsqrt() - T * torch.where(ok, c, one).rsqrt()
+    Ek = torch.where(ok, 0.5 * (diff ** 2).sum(dim=(2, 3), keepdim=True), one)
+    return Ek.mean(dim=(1, 2, 3))
+
+
+def gaussian_target_maps(points, R, sigma, reduce="max"):
+    """Target maps from several points per token: points [K, P, 2] ((row, col) in image fractions) -> [K, R, R], every point a
+    gaussian of width `sigma` map pixels by `optimize_token.gaussian_circle`'s formula, the P of a token combined by `reduce`
+    ("max", "sum" or "mean").  With target_energy="mse" this is keypoint guidance with several points per token; with P = 1 it is
+    the point form's target."""
+    from .optimize_token import gaussian_circle
+    points = torch.as_tensor(points)
+    if points.dim() != 3 or points.shape[-1] != 2 or 0 in points.shape or not points.is_floating_point():
+        raise ValueError(f"gaussian_target_maps: points {tuple(points.shape)} must be floating [K, P, 2]")
+    if reduce not in ("max", "sum", "mean"):
+        raise ValueError(f"gaussian_target_maps: reduce must be 'max', 'sum' or 'mean', got {reduce!r}")
+    each = torch.stack([gaussian_circle(points[k], size=int(R), sigma=sigma) for k in range(points.shape[0])])      # [K, P, R, R]
+    return each.amax(dim=1) if reduce == "max" else each.sum(dim=1) if reduce == "sum" else each.mean(dim=1)
+
+
+@torch.no_grad()
+def pose_targets(model, image, embedding, keypoint_indices, *, noise_level=-1, noise=None, layers=(0, 1, 2, 3)):
+    """The target maps of one or several example images -> [m, K, R, R] on the model's device: exactly the quantity the energy of
+    `keypoint_energy_grad` reads, the mean over the stored up-block cross layers `layers` and their heads of the up-res softmax
+    maps of the K tokens `keypoint_indices` -- of `image` ([3, H, W] or [m, 3, H, W] in [0, 1], or a numpy [m, H, W, 3]) noised to
+    `model.scheduler.timesteps[noise_level]` (`noise` [m, C, h, w]: the gaussian, drawn on the device when None) under the
+    learned `embedding` [1, T, D].  One noised forward through `find_pred_noise`, `collect_maps_batched(controller, indices=)` on
+    the device; no autograd; the hooked store is empty afterwards.  What the reference's generation script loads as
+    "example_attn_maps_indices.pt"."""
+    hooked = model.unet.__dict__.get("_skp_hook_controller")
+    if hooked is None or not hasattr(hooked, "step_store"):
+        raise RuntimeError("pose_targets: the UNet carries no attention store (register_attention_control / load_ldm)")
+    T = embedding.shape[1]
+    ids = [int(v) for v in torch.as_tensor(keypoint_indices).reshape(-1).tolist()]
+    if not ids or min(ids) < 0 or max(ids) >= T or len(set(ids)) != len(ids):
+        raise ValueError(f"keypoint_indices {ids} must be distinct ids of the embedding's {T} tokens")
+    dtype = next(model.unet.parameters()).dtype
+    hooked.reset()
+    try:
+        find_pred_noise(model, image, embedding.to(device=model.device, dtype=dtype), noise_level=noise_level, device=model.device,
+                        noise=noise)
+        chosen = [r for i, r in enumerate(hooked.step_store["attn"]) if i in layers]
+        if not chosen or not all(isinstance(r, FusedAttn) for r in chosen):
+            raise RuntimeError("pose_targets: no stored attention layer matches `layers` (or the store materialises its entries)")
+        if chosen[0].q.is_cuda and chosen[0].q.dtype == torch.float32:
+            from ._maps import collect_maps_batched
+            return collect_maps_batched(hooked, layers=layers, indices=torch.tensor(ids))
+        n, R, heads = chosen[0].q.shape[0], chosen[0].R, chosen[0].heads
+        M = sum(_materialize_host(r.q, r.k, heads, r.scale, R).reshape(n, heads, R * R, -1)[..., ids].mean(dim=1) for r in chosen)
+        return (M / len(chosen)).permute(0, 2, 1).reshape(n, len(ids), R, R).contiguous()
+    finally:
+        hooked.reset()
+
+
+def keypoint_energy_grad(model, latents, context, t, keypoints, indices, sigma, layers=(0, 1, 2, 3), doubled=False, *,
+                         target_maps=None, target_energy="cosine"):
     """Energy of keypoint guidance and its gradient by the latents at one timestep -> (pred_c, pred_u, E [n], g [n, C, h, w]).
     Runs the UNet forward(s) of `_predict` (`context = [uncond or None, cond]`, `doubled` as in `sampler_latent_step`) with autograd
     on, on a detached copy of `latents`; the maps M_i [K, R, R] of image i are the mean over the stored up-block cross layers
@@ -502,21 +628,38 @@ def keypoint_energy_grad(model, latents, context, t, keypoints, indices, sigma, 
     float32 device tensors take one node, `ops.MapPointLossFn` (fused maps for K rows, the point-loss kernel, the sparse map
     backward), and the HIP backward of the frozen UNet; host tensors and other dtypes the same formulas in torch ops, so the call
     runs on an fp64 copy of the modules on the host.  The model must be hooked (`register_attention_control`, as `load_ldm`
-    does)."""
+    does).
+    Pose transfer (keyword-only): `target_maps` [K, R', R'], [1, K, R', R'] or [n, K, R', R'] with `target_energy` "cosine" or "mse"
+    in place of `keypoints` (pass None; `sigma` is unused) -- the energy of the K maps against target MAPS,
+    `map_target_energy` / include/skp_targets.h: E_i = mean (M_i - T_i)^2, or (1/K) sum_k (1 - cos(M_ik, T_ik)), which does not
+    see the scale of either map.  Targets of another resolution are resampled to R (`resample_target_maps`).  The device node is
+    `ops.MapTargetLossFn`, the ledger site `sample.pose`."""
     n = latents.shape[0] // 2 if doubled else latents.shape[0]
     T = context[1].shape[1]
-    targets = _keypoint_targets(*_keypoint_ids(keypoints, indices, T), n, T, latents.device)
+    if target_maps is not None:
+        if keypoints is not None:
+            raise ValueError("keypoints and target_maps are mutually exclusive")
+        R = model.unet.__dict__.get("_skp_hook_res")
+        if R is None:
+            raise RuntimeError("keypoint_energy_grad: the UNet carries no attention store (register_attention_control / load_ldm)")
+        maps, ids = _target_map_ids(target_maps, target_energy, indices, T)
+        targets = _map_targets(maps, ids, target_energy, n, T, R, latents.device, latents.dtype)
+    else:
+        targets = _keypoint_targets(*_keypoint_ids(keypoints, indices, T), n, T, latents.device)
     return _energy_grad(model, latents, context, t, targets, sigma, layers, doubled)
 
 
 def _energy_grad(model, latents, context, t, targets, sigma, layers=(0, 1, 2, 3), doubled=False):
-    """`keypoint_energy_grad` for prepared `KeypointTargets` (the sampling loop makes them once, before its first step)."""
+    """`keypoint_energy_grad` for prepared `KeypointTargets` or `MapTargets` (the sampling loop makes them once, before its first
+    step)."""
     hooked = model.unet.__dict__.get("_skp_hook_controller")
     if hooked is None or not hasattr(hooked, "step_store"):
         raise RuntimeError("keypoint_energy_grad: the UNet carries no attention store (register_attention_control / load_ldm)")
     uncond, cond = context
     n = latents.shape[0] // 2 if doubled else latents.shape[0]
-    pos, ids, sel, tokrow = targets
+    to_maps = isinstance(targets, MapTargets)
+    site = "sample.pose" if to_maps else "sample.keypoints"
+    ids, sel, tokrow = targets.ids, targets.sel, targets.tokrow
     hooked.reset()
     records = []
     with torch.enable_grad():
@@ -527,12 +670,16 @@ def _energy_grad(model, latents, context, t, targets, sigma, layers=(0, 1, 2, 3)
             raise RuntimeError("keypoint_energy_grad: no stored attention layer matches `layers` (or the store materialises its "
                                "entries: AttentionStore(materialize=True) keeps no autograd history)")
         if x.is_cuda and x.dtype == torch.float32:
-            routes.note("sample.keypoints", "map_point_loss")
+            routes.note(site, "map_target_loss" if to_maps else "map_point_loss")
             st = stack_of(chosen, "keypoint_energy_grad", rows=slice(-n, None))   # the conditional rows: the last n of the forward
-            meta = dict(R=st.R, heads=st.heads, scales=st.scales, sigma=float(sigma), pos=pos, sel=sel, tokrow=tokrow)
-            E = ops.MapPointLossFn.apply(meta, *st.flat())
+            if to_maps:
+                meta = dict(R=st.R, heads=st.heads, scales=st.scales, target=targets.maps, mode=targets.mode, sel=sel, tokrow=tokrow)
+                E = ops.MapTargetLossFn.apply(meta, *st.flat())
+            else:
+                meta = dict(R=st.R, heads=st.heads, scales=st.scales, sigma=float(sigma), pos=targets.pos, sel=sel, tokrow=tokrow)
+                E = ops.MapPointLossFn.apply(meta, *st.flat())
         else:
-            routes.note("sample.keypoints", "host")
+            routes.note(site, "host")
             R, heads = chosen[0].R, chosen[0].heads
             M = 0
             for r in chosen:
@@ -540,10 +687,15 @@ def _energy_grad(model, latents, context, t, targets, sigma, layers=(0, 1, 2, 3)
                 probs = _materialize_host(r.q[-n:], k, heads, r.scale, R)     # (n * heads, R^2, T)
                 M = M + probs.reshape(n, heads, R * R, -1)[..., ids].mean(dim=1)
             M = (M / len(chosen)).permute(0, 2, 1).reshape(n, len(ids), R, R)
-            p = pos.to(M.dtype) * R
-            ar = torch.arange(R, device=M.device, dtype=M.dtype) + 0.5
-            d2 = (ar.view(1, 1, 1, R) - p[..., 1, None, None]) ** 2 + (ar.view(1, 1, R, 1) - p[..., 0, None, None]) ** 2
-            E = ((M - torch.exp(-d2 / (2.0 * float(sigma) ** 2))) ** 2).mean(dim=(1, 2, 3))
+            if to_maps:
+                if tuple(targets.maps.shape[1:]) != (len(ids), R, R):
+                    raise RuntimeError(f"keypoint_energy_grad: target maps {tuple(targets.maps.shape)} for maps {tuple(M.shape)}")
+                E = map_target_energy(M, targets.maps, targets.mode)
+            else:
+                p = targets.pos.to(M.dtype) * R
+                ar = torch.arange(R, device=M.device, dtype=M.dtype) + 0.5
+                d2 = (ar.view(1, 1, 1, R) - p[..., 1, None, None]) ** 2 + (ar.view(1, 1, R, 1) - p[..., 0, None, None]) ** 2
+                E = ((M - torch.exp(-d2 / (2.0 * float(sigma) ** 2))) ** 2).mean(dim=(1, 2, 3))
         g, = torch.autograd.grad(E.sum(), x)
     if doubled:
         g = g[n:]
@@ -702,8 +854,8 @@ def sample_graph_key(*, rows, doubled, two_forward, tokens, latent_shape, predic
     is kept doubled, whether guidance takes two forwards, the token counts (conditional, unconditional or None), the latent
     shape [C, h, w], the prediction type, the clamp, the kind of plan ("axpby" / "ddim_step": the call without a sampler;
     otherwise the sampler's name), whether an x0 history and per-step noise exist, K of the keypoints (0: none), the stored
-    layers the energy reads, `extra` (the energy's sigma and normalisation, which are arguments of recorded launches) and,
-    last, `tag`: `ops.frozen_tag` over the UNet's parameters, so a weight changed in place is another key."""
+    layers the energy reads, `extra` (the energy's sigma and normalisation, which are arguments of recorded launches; with
+    target maps ("maps", the energy mode, R, the rows of targets -- 1 or n --, the normalisation) instead) and, last, `tag`: `ops.frozen_tag` over the UNet's parameters, so a weight changed in place is another key."""
     return (int(rows), bool(doubled), bool(two_forward), tuple(None if t is None else int(t) for t in tokens),
             tuple(int(v) for v in latent_shape), str(prediction), bool(clip), str(kind), bool(history), bool(noise), int(keypoints),
             tuple(int(v) for v in layers), tuple(extra), tuple(tag))
@@ -753,8 +905,12 @@ class _RecordedStep:
         self.noise = None if noise is None else torch.zeros((cap,) + tuple(first.shape), **f32)
         self.targets = self.kscale = self.trace = None
         if targets is not None:
-            self.targets = KeypointTargets(torch.empty_like(targets.pos), list(targets.ids), torch.empty_like(targets.sel),
-                                           torch.empty_like(targets.tokrow))
+            if isinstance(targets, MapTargets):
+                self.targets = MapTargets(torch.empty_like(targets.maps), targets.mode, list(targets.ids),
+                                          torch.empty_like(targets.sel), torch.empty_like(targets.tokrow))
+            else:
+                self.targets = KeypointTargets(torch.empty_like(targets.pos), list(targets.ids), torch.empty_like(targets.sel),
+                                               torch.empty_like(targets.tokrow))
             self.kscale = torch.zeros(cap, **f32)
             self.trace = torch.zeros(cap, n, **f32)
         self.graphs = {}                                         # "plain" / "kp" -> (graph, held values, route notes of one replay)
@@ -776,7 +932,10 @@ class _RecordedStep:
         if self.hist is not None:
             self.hist.copy_(x0_hist)
         if self.targets is not None:
-            self.targets.pos.copy_(targets.pos)
+            if isinstance(targets, MapTargets):
+                self.targets.maps.copy_(targets.maps)
+            else:
+                self.targets.pos.copy_(targets.pos)
             self.targets.sel.copy_(targets.sel)
             self.targets.tokrow.copy_(targets.tokrow)
             self.targets.ids[:] = targets.ids
@@ -917,7 +1076,10 @@ def _captured_steps(model, controller, latents, context, ts, at, guidance_scale,
     layers, extra, needs = (0, 1, 2, 3), (), ["plain"] * steps
     if targets is not None:
         lo, hi, kscale, sigma, normalize, trace = kp
-        extra = (float(sigma), bool(normalize))
+        if isinstance(targets, MapTargets):                      # the kind of target, the energy's kernels, the static buffer's shape
+            sigma, extra = 0.0, ("maps", targets.mode, int(targets.maps.shape[-1]), int(targets.maps.shape[0]), bool(normalize))
+        else:
+            extra = (float(sigma), bool(normalize))
         needs = ["kp" if lo <= i / steps < hi else "plain" for i in range(steps)]
     key = sample_graph_key(rows=n, doubled=doubled, two_forward=guided and not doubled,
                            tokens=(context[1].shape[1], context[0].shape[1] if guided else None), latent_shape=latents.shape[1:],
@@ -933,8 +1095,8 @@ def _captured_steps(model, controller, latents, context, ts, at, guidance_scale,
         hit = None
     try:
         step = hit if hit is not None else _RecordedStep(model, key, latents, context, x0_hist, noise, targets, steps, kind,
-                                                            prediction, clip, extra[0] if extra else 0.0,
-                                                            extra[1] if extra else False, layers)
+                                                            prediction, clip, float(sigma) if extra else 0.0,
+                                                            bool(normalize) if extra else False, layers)
         ks = None if targets is None else torch.tensor([float(kscale) * c.sb for c in coefs], dtype=torch.float64).to(torch.float32)
         step.stage(latents, context, pack_step_table(coefs, guidance_scale), torch.as_tensor(ts), noise, x0_hist, targets, ks, at)
         missing = [w for w in sorted(set(needs[at:])) if w not in step.graphs]
@@ -970,7 +1132,8 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
                           uncond_embedding: Optional[torch.Tensor] = None, uncond_prompt: Optional[str] = None,
                           sampler: Optional[str] = None, eta: float = 0.0, keypoints=None, keypoint_indices=None,
                           keypoint_scale: float = 2.0, keypoint_sigma: float = 2.0, keypoint_steps=(0.0, 1.0),
-                          keypoint_normalize: bool = True, keypoint_trace: Optional[list] = None, capture: bool = False):
+                          keypoint_normalize: bool = True, keypoint_trace: Optional[list] = None, capture: bool = False,
+                          target_maps=None, target_energy: str = "cosine"):
     """ptp_utils.py:420-461: sample an image from the learned `embedding` [1, T, D] by `num_inference_steps` steps of `sampler`
     (deterministic DDIM by default) and decode it -> (image, latent).  `image`: uint8 numpy [1, height, width, 3] (`output_type="uint8"`) or the float32
     tensor [1, 3, height, width] in [0, 1] on the model's device before the 8-bit rounding (`"float"`); `latent`: the initial
@@ -1013,12 +1176,26 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
     tried on the seeded reduced-width tree of the tests, never on trained weights.  ValueError: one of the two without the other,
     a shape mismatch, an index outside the embedding (or twice).  Without `keypoints` nothing changes: the same routes, the same
     bits.
+    Pose transfer (keyword-only extension): `target_maps` [K, R', R'], [1, K, R', R'] (the same targets for every image) or
+    [n, K, R', R'] with `keypoint_indices`, in place of `keypoints` (ValueError if both are given), guides toward target MAPS --
+    those of an example image from `pose_targets`, "sample an image in the pose of this photo", or several points per token
+    from `gaussian_target_maps` -- instead of one gaussian per token: the other file the reference's script loads and never
+    uses.  `target_energy`: "cosine" (the default) -- E_i = (1/K) sum_k (1 - cos(M_ik, T_ik)), blind to the scale of either map,
+    which the example's maps and the sample's, taken at different noise levels, need not share; a map of zeros counts 1 -- or
+    "mse" -- E_i = mean (M_i - T_i)^2, the reference's `find_gaussian_loss_at_point` with the target handed in
+    (include/skp_targets.h, `map_target_energy`).  Targets of another resolution are resampled to the model's R once per call
+    (`resample_target_maps`: one library call, plumbing).  `keypoint_scale`, `keypoint_steps`, `keypoint_normalize`,
+    `keypoint_trace` and the step-kernel term mean what they mean above; `keypoint_sigma` is unused.  Like it, the default scale
+    was only tried on the seeded reduced-width tree of the tests, for either energy.  ValueError, before anything is drawn from a
+    generator: maps without indices, a wrong K, rows that are neither 1 nor n, maps that are not square, an unknown energy.
+    Ledger site `sample.pose`.  Without `target_maps` nothing changes.
     `capture=True` (keyword-only extension; off by default, and then every route, bit and ledger note is what it was): on a float32
     GPU model the first two steps run as always, then ONE step is recorded as a graph over static buffers and replayed for every
     remaining step with no host work in between -- the per-step scalars, the timestep's sinusoid row, the noise row and the
     keypoint scale are read from device tables by a device counter (include/skp_sampler_graph.h, `ops.sampler_step_dev`), so the
     replays compute what the eager launches compute, bit for bit.  With keypoints the guided step is a second graph over the same
-    buffers and the host picks one per step.  Graphs and buffers are kept on the model (`sample_graphs(model)`, with `clear()`),
+    buffers and the host picks one per step; target maps ride in a static buffer like the positions, and their kind, energy,
+    R and row count are part of the key (other target VALUES replay the same graph).  Graphs and buffers are kept on the model (`sample_graphs(model)`, with `clear()`),
     keyed by `sample_graph_key` and the frozen tag of the UNet's weights; a later call with the same key refreshes the buffers and
     replays.  Calls of fewer than three steps, a controller with its own `step_callback` (one warning), the clamped default step
     and a key whose recording failed (one warning, never retried) stay on eager launches; host tensors take the host route.
@@ -1055,7 +1232,20 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
         if isinstance(uncond_embedding, tuple):                    # SDXL: (context, pooled); the pooled vector is not fed to sampling
             uncond_embedding = uncond_embedding[0]
     targets = None
-    if keypoints is not None or keypoint_indices is not None:           # (checked before anything is drawn from a generator)
+    if target_maps is not None:                                         # (checked before anything is drawn from a generator)
+        if keypoints is not None:
+            raise ValueError("text2image_ldm_stable: keypoints and target_maps are mutually exclusive")
+        targets = _target_map_ids(target_maps, target_energy, keypoint_indices, embedding.shape[1])
+        rows = len(generator) if isinstance(generator, (list, tuple)) else \
+            latent.shape[0] if latent is not None and latent.dim() == 4 else 1
+        if targets[0].shape[0] not in (1, rows):
+            raise ValueError(f"target_maps {tuple(targets[0].shape)}: {targets[0].shape[0]} rows of targets for {rows} images")
+        map_res = model.unet.__dict__.get("_skp_hook_res")
+        if map_res is None:
+            raise RuntimeError("text2image_ldm_stable(target_maps=...): the UNet carries no attention store "
+                               "(register_attention_control / load_ldm)")
+        lo, hi = (float(v) for v in keypoint_steps)
+    elif keypoints is not None or keypoint_indices is not None:
         targets = _keypoint_ids(keypoints, keypoint_indices, embedding.shape[1])
         lo, hi = (float(v) for v in keypoint_steps)
     if isinstance(generator, (list, tuple)) or (latent is not None and latent.dim() == 4 and latent.shape[0] != 1):
@@ -1076,7 +1266,10 @@ def text2image_ldm_stable(model, embedding, controller, num_inference_steps: int
             raise ValueError(f"uncond_embedding {tuple(uncond_embedding.shape)} must be [1, T, {embedding.shape[-1]}]")
     context = [uncond if guided else None, embedding]
     if targets is not None:
-        targets = _keypoint_targets(*targets, n, embedding.shape[1], latents.device)
+        if target_maps is not None:
+            targets = _map_targets(*targets, target_energy, n, embedding.shape[1], map_res, latents.device, latents.dtype)
+        else:
+            targets = _keypoint_targets(*targets, n, embedding.shape[1], latents.device)
         if plan is None:
             plan = SamplerPlan(model.scheduler, "ddim", 0.0)       # the guided step is a term of the sampler kernel
     # on the GPU a guided step with contexts of equal length keeps the 2n-row UNet input between steps (written by the step kernel)

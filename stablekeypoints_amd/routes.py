@@ -79,6 +79,9 @@ ROUTES: Dict[str, Dict[str, str]] = {
     # energy and latent gradient of keypoint guidance (ptp_utils.keypoint_energy_grad): the fused maps + point-loss node
     # (ops.MapPointLossFn; its map kernels note `map.fwd` / `map.bwd` as well) / torch ops on host tensors and other dtypes
     "sample.keypoints": {"map_point_loss": "hip", "host": "host"},
+    # the same with target MAPS (pose transfer: keypoint_energy_grad with `MapTargets`, text2image_ldm_stable(target_maps=)): the fused
+    # maps + target-loss node (ops.MapTargetLossFn) / the two formulas of include/skp_targets.h in torch ops on host tensors
+    "sample.pose": {"map_target_loss": "hip", "host": "host"},
     # visualize.overlay: (min, max) of every heat map, and images + maps + points -> bytes in a canvas: the range and overlay
     # kernels (ops.map_range, ops.overlay_u8) / visualize.range_formula, visualize.overlay_formula in torch on host tensors
     "visualize.range": {"map_range": "hip", "host": "host"},

@@ -4,7 +4,7 @@ classifier-free guidance, and print the route table of one guided step.
 
     python tools/generate_bench.py [--model synthetic-sd15] [--size 512] [--steps 10] [--n 4] [--rounds 3] [--tokens 77] [--json FILE]
                                    [--sampler ddim|dpm++2m|dpm++2m-sde [--eta 0] [--sampler-steps K]] [--variants A,G1] [--keypoints]
-                                   [--capture]
+                                   [--pose] [--capture]
 
 Every timed call ends in a device synchronise (the uint8 image is copied to the host); every shape is warmed up once before the
 timed rounds; the variants run alternately inside each round, so a drift of the machine shows up as spread, not as a difference.
@@ -20,6 +20,11 @@ drawn from the seed, every step guided), in turn with the call without it (with 
 timed against the route the package had before it -- dense fused maps under autograd, a gather, torch ops for the target and the
 MSE -- on the hooked layers of SD-1.5 at 512^2 (sides 16, 16, 16, 32; 8 heads of 160, 160, 160, 80 channels; R = 128) with
 T = 77 and T = 500 tokens, K = 10, n = 1 and 4 rows.
+`--pose`: every variant is timed as `<variant>+kp` (as with `--keypoints`) and, in turn with it, as `<variant>+pose` and
+`<variant>+pose-mse`: the same call guided toward target MAPS (`target_maps=`, the cosine and the mse energy) -- the maps
+`ptp_utils.pose_targets` takes from a random image for the same K = 10 tokens, one target for every image -- so the pose-guided
+call stands next to the point-guided call of the same shape; and the energy kernels alone, `ops.map_target_loss` (both modes)
+against `ops.point_loss`, at K = 10, R = 128 with 1 and 4 rows and at K = 3, R = 32 with 2 rows.
 `--capture`: every variant (those of the other flags included) is timed a second time as `<variant>+graph`, the same call with
 `capture=True` -- two steps on eager launches, the rest as replays of one recorded step -- in turn with the eager call; the
 warm-up call of each variant is timed too and printed as `first call`: for a `+graph` variant it holds the one-off cost of
@@ -49,6 +54,7 @@ def main():
     ap.add_argument("--sampler-steps", type=int, default=None)
     ap.add_argument("--variants", default=None)
     ap.add_argument("--keypoints", action="store_true")
+    ap.add_argument("--pose", action="store_true")
     ap.add_argument("--capture", action="store_true")
     a = ap.parse_args()
     import torch
@@ -94,10 +100,17 @@ def main():
     if a.sampler is not None:
         k_steps = a.sampler_steps or a.steps
         overs[f"@{a.sampler}/{k_steps}"] = dict(sampler=a.sampler, eta=a.eta, num_inference_steps=k_steps)
-    if a.keypoints:
+    if a.keypoints or a.pose:
         kp_ids = torch.randperm(a.tokens, generator=g)[:10].sort().values
         kp = dict(keypoints=torch.rand(len(kp_ids), 2, generator=g), keypoint_indices=kp_ids)
-        overs = {name: o for suffix, over in overs.items() for name, o in ((suffix, over), (suffix + "+kp", {**over, **kp}))}
+        guided = [("+kp", kp)]
+        if a.pose:
+            example = torch.rand(1, 3, a.size, a.size, generator=g)
+            maps = ptp_utils.pose_targets(ldm, example, cond, kp_ids)
+            guided += [("+pose", dict(target_maps=maps, target_energy="cosine", keypoint_indices=kp_ids)),
+                       ("+pose-mse", dict(target_maps=maps, target_energy="mse", keypoint_indices=kp_ids))]
+        overs = {name: o for suffix, over in overs.items()
+                 for name, o in [(suffix, over)] + [(suffix + tail, {**over, **extra}) for tail, extra in guided]}
     if a.capture:
         overs = {name: o for suffix, over in overs.items() for name, o in ((suffix, over), (suffix + "+graph", {**over, "capture": True}))}
     made = {suffix: make(**over) for suffix, over in overs.items()}
@@ -138,10 +151,41 @@ def main():
         tables[2 * rows] = routes.table(routes.delta(before))
         print(f"\nroutes of one guided step, {2 * rows} rows per forward:\n{tables[2 * rows]}")
     node = node_against_older_route(a.rounds) if a.keypoints else {}
+    energy = target_loss_against_point_loss(a.rounds) if a.pose else {}
     if a.json:
         with open(a.json, "w") as f:
             json.dump(dict(args=vars(a), seconds_per_image=times, first_call_seconds=first, routes={str(k): v for k, v in tables.items()},
-                           map_point_loss_seconds=node), f, indent=1)
+                           map_point_loss_seconds=node, energy_kernel_seconds=energy), f, indent=1)
+
+
+def target_loss_against_point_loss(rounds, calls=200):
+    """`ops.map_target_loss` (mse, cosine; a shared target) against `ops.point_loss` on random maps of softmax scale; `calls` of each
+    per timed window, the three in turn; -> {shape: {kernel: [seconds per call]}}."""
+    import torch
+    from stablekeypoints_amd import ops
+    out = {}
+    for B, K, R in ((1, 10, 128), (4, 10, 128), (2, 3, 32)):
+        g = torch.Generator().manual_seed(B + K + R)
+        M = (torch.rand(B, K, R, R, generator=g) / 77).cuda()
+        T = (torch.rand(1, K, R, R, generator=g) / 77).cuda()
+        pos = torch.rand(B, K, 2, generator=g).cuda()
+        fns = {"point_loss": lambda: ops.point_loss(M, pos, 2.0), "map_target_loss mse": lambda: ops.map_target_loss(M, T, "mse"),
+               "map_target_loss cosine": lambda: ops.map_target_loss(M, T, "cosine")}
+        times = {k: [] for k in fns}
+        for fn in fns.values():
+            fn()
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) / calls)
+        out[f"B={B} K={K} R={R}"] = times
+        print(f"energy and unit gradient, B = {B}, K = {K}, R = {R}: " + ", ".join(
+            f"{k} median {sorted(ts)[len(ts) // 2] * 1e6:.1f} us (min {min(ts) * 1e6:.1f})" for k, ts in times.items()))
+    return out
 
 
 def node_against_older_route(rounds, K=10, R=128, sides=(16, 16, 16, 32), heads=8, widths=(1280, 1280, 1280, 640), calls=20):
